@@ -2,6 +2,7 @@
 """bench.py -- TripolarGrid metric precompute + zipper halo fill at 1/10 deg x 75 levels on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--exchange auto|monolithic|pipelined_1|pipelined_2]
+  python bench.py [--steps K] [--warmup W] [--full] [--dump-outputs DIR]                   (N = 1: --full = every figure beyond the headline)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...     (same thing, launcher supplied)
   python bench.py --loopback [--loopback-bands R] [--loopback-band r]                          (1 GPU: the RCCL branch on one rank)
 
@@ -19,11 +20,13 @@ peers are the rank itself: a rehearsal of the code path, not a scaling measureme
 
 Order of a run (N = 1): set-up -> the DECLARED clock pre-roll (`clock_preroll`: P plain tpg_build_grid calls, ~35 ms, so that a short
 run starts from the sustained FP64 clock state; `--preroll 0` = none) -> exactly W untimed warm-up steps -> exactly K timed steps
-(`value`, `ms_per_step`) -> untimed instrumented passes (per-phase breakdown, the fold-only pass behind `roofline_fold`) -> K steps
+(`value`, `ms_per_step`, and `fill_ms` / `roofline` from the fill kernel's own events in those steps) -> with `--dump-outputs DIR`, a
+fixed sample of what the last timed step computed (dump_indices) -> the line.  That is a plain run.  `--full` goes on, after the timed
+steps: untimed instrumented passes (per-phase breakdown, the fold-only pass behind `roofline_fold`) -> K steps
 started right after >= 50 ms of HBM-bound work, no pre-roll, no warm-up (`ms_per_step_cold_onset`: what a caller's FIRST builds cost)
 -> the auxiliary measurements (fold / fill by cache state, copy ceiling, the 8- and 16-field batched fold, Float32, config 2, geometry,
 config 5 at halo 4 = `fill_step`, and the halo fills at the reference's own model halo (5, 5, 5) = `fill_step_halo5`) -> cpu_baseline.
-Nothing optional precedes the timed region: `value` is the same with --no-aux / --no-fill-step.
+Nothing optional precedes the timed region: `value` is the same with or without --full, --no-aux / --no-fill-step.
 
 value = horizontal grid cells / step time.  `roofline` is the halo-fill kernel the step launches (k_fill_merged: the zipper halo fill as
 the product issues it, HBM-bound); `roofline_fold` is the fold alone (k_zipper_cols, the kernel BASELINE.json's north_star puts the
@@ -110,6 +113,43 @@ def cpu_baseline():
     }
 
 
+DUMP_SEED = 0x5EED
+DUMP_GRID, DUMP_HALO, DUMP_INTERIOR = 1 << 17, 1 << 19, 1 << 16      # float64 elements per dumped array: ~40 MB in all
+
+
+def dump_indices():
+    """The fixed, seeded sample `--dump-outputs` writes, as sorted flat indices: `grid` into each padded (NY+2H) x (NX+2H) grid array;
+    `halo` into a (NZ+2H, NY+2H, NX+2H) field, among the x/y halo cells of every level (what the fill writes); `interior` into the
+    same field, among the x/y interior cells of every level (what the fill reads; the zipper's row-Ny substitution among them)."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    rows, cols, levels = NY + 2 * H, NX + 2 * H, NZ + 2 * H
+    inner = np.zeros((rows, cols), dtype=bool)
+    inner[H:H + NY, H:H + NX] = True
+
+    def every_level(xy, n):
+        k = np.sort(rng.choice(levels * xy.size, n, replace=False))
+        return (k // xy.size) * (rows * cols) + xy[k % xy.size]
+
+    grid = np.sort(rng.choice(rows * cols, DUMP_GRID, replace=False))
+    return grid, every_level(np.flatnonzero(~inner), DUMP_HALO), every_level(np.flatnonzero(inner), DUMP_INTERIOR)
+
+
+def dump_outputs(dirname, torch, dev, out, fields):
+    """--dump-outputs DIR: what the last timed step handed its caller, sampled at dump_indices(): DIR/grid_<array>.npy for the 20 arrays of
+    tpg_build_grid, DIR/<field>_halo.npy and DIR/<field>_interior.npy for the 4 fields after tpg_fill_halo_regions (float64)."""
+    import numpy as np
+    from orthogonalsphericalshellgrids.jl_amd import _lib
+    grid, halo, interior = (torch.from_numpy(i).to(dev) for i in dump_indices())
+    sample = {f"grid_{name}": torch.take(a, grid) for name, a in zip(_lib.ARRAY_NAMES, out)}
+    for (name, *_), f in zip(SPECS, fields):
+        sample[f"{name}_halo"] = torch.take(f, halo)
+        sample[f"{name}_interior"] = torch.take(f, interior)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in sample.items():
+        np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy())
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -129,10 +169,15 @@ def parse_args():
                     help="seconds allowed for the process-group rendezvous + RCCL communicator creation (covers a cold `import torch` on every rank)")
     ap.add_argument("--preroll", type=int, default=-1,
                     help="plain tpg_build_grid calls before the warm-up steps (the declared clock pre-roll); default 64 per 1800 rows of band, 0 = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fill-step", action="store_true", help="skip the config-5 (1/24 deg x 100 levels) measurements fill_step and fill_step_halo5")
-    ap.add_argument("--no-cold-onset", action="store_true", help="skip the K cold-onset steps (profiling passes: keeps the 100 streaming launches out of the trace)")
-    ap.add_argument("--no-aux", action="store_true", help="skip the auxiliary measurements (cache states, copy ceiling, Float32, config 2, geometry)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also run everything beyond the headline figure (per-phase and fold-only passes, cold onset, "
+                         "auxiliary measurements, config 5, cpu_baseline); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write a fixed, seeded sample of what the last timed step computed (grid arrays, filled fields) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-fill-step", action="store_true", help="--full: skip the config-5 (1/24 deg x 100 levels) measurements fill_step and fill_step_halo5")
+    ap.add_argument("--no-cold-onset", action="store_true", help="--full: skip the K cold-onset steps (profiling passes: keeps the 100 streaming launches out of the trace)")
+    ap.add_argument("--no-aux", action="store_true", help="--full: skip the auxiliary measurements (cache states, copy ceiling, Float32, config 2, geometry)")
     return ap.parse_args()
 
 
@@ -142,6 +187,8 @@ def main():
         raise SystemExit("--loopback is a one-GPU mode (--gpus 1)")
     if args.loopback and not (0 <= args.loopback_band < args.loopback_bands and args.loopback_bands >= 2):
         raise SystemExit("--loopback-band must lie in 0 .. --loopback-bands - 1 (bands >= 2)")
+    if args.dump_outputs and (args.gpus > 1 or args.loopback):
+        raise SystemExit("--dump-outputs is an N = 1 option (--gpus 1, no --loopback)")
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1") or "1") == 1:
         # no launcher (WORLD_SIZE unset, or a single-process environment that exports WORLD_SIZE=1): become one.  Checked BEFORE torch is
         # imported or a device is touched.
@@ -174,7 +221,7 @@ def main():
 
 
 def run_single(args):
-    """N = 1: the step on cuda:LOCAL_RANK, every figure of the contract line"""
+    """N = 1: the step on cuda:LOCAL_RANK; the contract line, and with --full every other figure of it"""
     import torch
     import orthogonalsphericalshellgrids.jl_amd as osg
     from orthogonalsphericalshellgrids.jl_amd import _lib
@@ -263,7 +310,49 @@ def run_single(args):
         step(kevs[k])
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    fill_live = [elapsed_ms(e0, e1) for e0, e1 in kevs]
+    t_fill_kernel = sum(fill_live) / len(fill_live)                                 # the merged kernel's own duration, timed steps
+    for e0, e1 in kevs:
+        lib.tpg_event_destroy(e0); lib.tpg_event_destroy(e1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, dev, out, fields)
 
+    # ---- the line: what the timed steps measured ---------------------------------------------------------------------------------------------
+    ms_per_step = elapsed / args.steps * 1e3
+    cells = NX * NY
+    zbytes = sum(zipper_algorithmic_bytes(NX, NZ, H).values())
+    pbytes = periodic_algorithmic_bytes(NY, NZ, H, n)
+    fill_bytes = zbytes + pbytes
+    band_cells = (NY + 2 * H) * (NX + 2 * H)
+    line = {
+        "metric": METRIC,
+        "value": cells / (elapsed / args.steps), "unit": "cells/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "TripolarGrid 1/10deg metric precompute (3600x1800, Float64, halo 4) + fill_halo_regions! of 4 fields "
+                               "c/u/v/zeta (3600x1800x75): zipper + periodic-x in one merged launch",
+                   "global_size": [NX, NY, NZ], "local_size": [NX, NY, NZ], "rows_per_rank": NY, "halo": [H, H, H],
+                   "fields": [s[0] for s in SPECS], "parallelism": "latitude-bands x1"},
+        "clock_preroll": preroll,
+        "fill_ms": t_fill_kernel, "fill_GBps": fill_bytes / (t_fill_kernel * 1e-3) / 1e9,
+    }
+    traffic = load_traffic()
+    tm = traffic.get("k_fill_merged")
+    line["roofline"] = {
+        "kernel": "k_fill_merged<double,2,4> (tpg_fill_halo_regions: 4 fields x 83 levels, zipper fold + periodic x, one launch)", "bound": "hbm",
+        "achieved": fill_bytes / (t_fill_kernel * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+        "frac": fill_bytes / (t_fill_kernel * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": tm,
+        "algorithmic_bytes_per_launch": fill_bytes, "algorithmic_bytes_fold": zbytes, "algorithmic_bytes_periodic_x": pbytes,
+        "launch_ms": t_fill_kernel, "measured": "the kernel's own start/stop events on every timed step (hipExtLaunchKernelGGL)",
+        "launch_ms_median_min_max": [statistics.median(fill_live), min(fill_live), max(fill_live)],
+        "traffic_frac": (tm / (t_fill_kernel * 1e-3) / 1e9 / HBM_PEAK_GBPS) if tm else None,
+        "note": "the periodic-x part moves 128 B per row but must fetch and dirty 3 whole 128-B lines per row pair (row pitch 225.5 lines): "
+                "counter traffic is ~1.5x algorithmic and the launch sits at the device's line rate (DESIGN.md 6)"}
+    if not args.full:
+        return line
+
+    # ==== --full: everything below runs after the timed steps and adds keys to the line ========================================================
     # ---- untimed instrumented pass: K steps with stream markers around the two phases ----------------------------------------------
     marks = [[ev() for _ in range(3)] for _ in range(args.steps)]
     for k in range(args.steps):
@@ -272,10 +361,6 @@ def run_single(args):
     torch.cuda.synchronize()
     avg = lambda a, b: sum(m[a].elapsed_time(m[b]) for m in marks) / len(marks)      # ms
     t_build, t_fill_bracket = avg(0, 1), avg(1, 2)
-    fill_live = [elapsed_ms(e0, e1) for e0, e1 in kevs]
-    t_fill_kernel = sum(fill_live) / len(fill_live)                                 # the merged kernel's own duration, timed steps
-    for e0, e1 in kevs:
-        lib.tpg_event_destroy(e0); lib.tpg_event_destroy(e1)
 
     # ---- fold-only pass, K old-style steps (build -> tpg_zipper_fill [k_zipper_cols] -> tpg_periodic_x_fill) ----------------------
     fevs = [(hip_event(), hip_event()) for _ in range(args.steps)]
@@ -320,45 +405,16 @@ def run_single(args):
         fill_step = bench_aux.fill_step_config5(torch, osg, _lib, tlib, dev)
         fill_step_halo5 = bench_aux.fill_step_halo5(torch, osg, _lib, lib, tlib, dev)
 
-    # ---- the line ------------------------------------------------------------------------------------------------------------------------------
-    ms_per_step = elapsed / args.steps * 1e3
-    cells = NX * NY
-    zbytes = sum(zipper_algorithmic_bytes(NX, NZ, H).values())
-    pbytes = periodic_algorithmic_bytes(NY, NZ, H, n)
-    fill_bytes = zbytes + pbytes
-    band_cells = (NY + 2 * H) * (NX + 2 * H)
-    line = {
-        "metric": METRIC,
-        "value": cells / (elapsed / args.steps), "unit": "cells/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "TripolarGrid 1/10deg metric precompute (3600x1800, Float64, halo 4) + fill_halo_regions! of 4 fields "
-                               "c/u/v/zeta (3600x1800x75): zipper + periodic-x in one merged launch",
-                   "global_size": [NX, NY, NZ], "local_size": [NX, NY, NZ], "rows_per_rank": NY, "halo": [H, H, H],
-                   "fields": [s[0] for s in SPECS], "parallelism": "latitude-bands x1"},
-        "clock_preroll": preroll,
+    # ---- the --full keys of the line ------------------------------------------------------------------------------------------------------------
+    line.update({
         "ms_per_step_cold_onset": cold_onset["ms_per_step"] if cold_onset else None, "cold_onset": cold_onset,
         "precompute_cells_per_s": cells / (t_build * 1e-3),
-        "precompute_ms": t_build, "fill_ms": t_fill_kernel, "fill_bracket_ms": t_fill_bracket,
-        "fill_GBps": fill_bytes / (t_fill_kernel * 1e-3) / 1e9,
-    }
+        "precompute_ms": t_build, "fill_bracket_ms": t_fill_bracket,
+    })
     line.update(aux)
     if fill_step is not None:
         line["fill_step"] = fill_step
         line["fill_step_halo5"] = fill_step_halo5
-    traffic = load_traffic()
-    tm = traffic.get("k_fill_merged")
-    line["roofline"] = {
-        "kernel": "k_fill_merged<double,2,4> (tpg_fill_halo_regions: 4 fields x 83 levels, zipper fold + periodic x, one launch)", "bound": "hbm",
-        "achieved": fill_bytes / (t_fill_kernel * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-        "frac": fill_bytes / (t_fill_kernel * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": tm,
-        "algorithmic_bytes_per_launch": fill_bytes, "algorithmic_bytes_fold": zbytes, "algorithmic_bytes_periodic_x": pbytes,
-        "launch_ms": t_fill_kernel, "measured": "the kernel's own start/stop events on every timed step (hipExtLaunchKernelGGL)",
-        "launch_ms_median_min_max": [statistics.median(fill_live), min(fill_live), max(fill_live)],
-        "traffic_frac": (tm / (t_fill_kernel * 1e-3) / 1e9 / HBM_PEAK_GBPS) if tm else None,
-        "note": "the periodic-x part moves 128 B per row but must fetch and dirty 3 whole 128-B lines per row pair (row pitch 225.5 lines): "
-                "counter traffic is ~1.5x algorithmic and the launch sits at the device's line rate (DESIGN.md 6)"}
     line["roofline_fold"] = {
         "kernel": "k_zipper_cols<double,2,4> (tpg_zipper_fill: the fold alone, 4 fields x 75 levels, one launch)", "bound": "hbm",
         "achieved": zbytes / (fold * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",

@@ -1,5 +1,5 @@
-"""bench.py's output contract: exactly one JSON line on stdout with the driver's keys, the `roofline`
-object of the dominant HBM-bound kernel and the `cpu_baseline` object (bounded oracle sample)."""
+"""bench.py's output contract: exactly one JSON line on stdout with the driver's keys and the `roofline` object of the
+dominant HBM-bound kernel; with --full also the `cpu_baseline` object (bounded oracle sample) and every other figure."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_contract_line(gpu):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preroll", "8"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--preroll", "8", "--full"],
                        cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -89,6 +89,64 @@ def test_bench_prints_one_contract_line(gpu):
     assert f32["halo5"]["fill_first_kernel_ms"] > 0.6 * f32["halo5"]["fill_ms"]
     if "skipped" not in h5.get("config5_halo5", {"skipped": 1}):
         assert h5["config5_halo5"]["fields_GB"] > 164 and 0.7 < h5["config5_time_per_byte_halo5_over_halo4"] < 1.25
+
+
+FULL_ONLY = ("cpu_baseline", "roofline_fold", "roofline_precompute", "cold_onset", "ms_per_step_cold_onset", "precompute_ms", "fill_bracket_ms",
+             "zipper_cold_ms", "float32", "roofline_fold_batched", "config2_quarter_degree_build", "fill_step", "fill_step_halo5")
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(gpu, oracle, tmp_path):
+    """A plain run (no --full) is the headline alone: the same contract keys, nothing the --full passes measure.  --dump-outputs writes
+    a fixed sample of the last timed step's outputs that does not depend on --steps / --warmup: the grid arrays as the oracle builds
+    them (<= 1e-12 relative), the fields' interior as the synthetic input, their periodic-x halo as the interior it copies."""
+    import numpy as np
+    import bench
+    from helpers import max_rel_err, splitmix64
+    for steps, warmup in ((2, 1), (5, 0)):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--dump-outputs", str(tmp_path / f"s{steps}")], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, out
+        d = json.loads(out[0])
+        assert d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == 1 and d["unit"] == "cells/s" and d["dtype"] == "f64"
+        assert d["higher_is_better"] is True and abs(d["value"] - 3600 * 1800 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["roofline"]["launch_ms"] == d["fill_ms"] > 0 and d["clock_preroll"]["builds"] == 64
+        assert not [k for k in FULL_ONLY if k in d], [k for k in FULL_ONLY if k in d]
+    names = sorted(f.name for f in (tmp_path / "s2").iterdir())
+    assert names == sorted(f.name for f in (tmp_path / "s5").iterdir()) and len(names) == 20 + 2 * 4
+    assert sum((tmp_path / "s2" / n).stat().st_size for n in names) <= 64 << 20
+    dumps = {n[:-4]: np.load(tmp_path / "s2" / n) for n in names}
+    for n, a in dumps.items():                                                   # the same inputs, the same outputs, whatever K and W
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "s5" / (n + ".npy"))), n
+    g_idx, halo_idx, in_idx = bench.dump_indices()
+    ref = oracle.build_grid((3600, 1800, 75))
+    for name, r in ref.items():
+        err, _ = max_rel_err(dumps["grid_" + name], r.reshape(-1)[g_idx])
+        assert err <= 1e-12, (name, err)
+    (Nx, Ny, Nz), H = (3600, 1800, 75), 4
+    cols, plane = Nx + 2 * H, (Ny + 2 * H) * (Nx + 2 * H)
+
+    def synthetic(seed, idx):                                                    # tests/helpers.synthetic_field at flat indices
+        k, rem = np.divmod(idx, plane)
+        j, i = np.divmod(rem, cols)
+        with np.errstate(over="ignore"):
+            h = splitmix64(np.uint64(seed) ^ splitmix64(idx.astype(np.uint64)))
+        v = ((h >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -52 - 1.0
+        inside = (k >= H) & (k < H + Nz) & (j >= H) & (j < H + Ny) & (i >= H) & (i < H + Nx)
+        return np.where(inside, v, 12345.0)
+
+    for fid, name in enumerate(("c", "u", "v", "zeta")):
+        j = (in_idx % plane) // cols
+        keep = j < H + Ny - 1                                                    # row Ny: the zipper's substitution for c / u
+        assert np.array_equal(dumps[name + "_interior"][keep], synthetic(0x5EED + fid, in_idx[keep])), name
+        k, rem = np.divmod(halo_idx, plane)
+        j, i = np.divmod(rem, cols)
+        west = (k >= H) & (k < H + Nz) & (j >= H) & (j < H + Ny - 1) & (i < H)
+        east = (k >= H) & (k < H + Nz) & (j >= H) & (j < H + Ny - 1) & (i >= H + Nx)
+        assert west.sum() > 1000 and east.sum() > 1000
+        assert np.array_equal(dumps[name + "_halo"][west], synthetic(0x5EED + fid, halo_idx[west] + Nx)), name
+        assert np.array_equal(dumps[name + "_halo"][east], synthetic(0x5EED + fid, halo_idx[east] - Nx)), name
 
 
 def _two_rank_bench(extra, launcher="self", ranks=2):

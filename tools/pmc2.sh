@@ -4,7 +4,7 @@ TAG=$1; shift
 REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out/pmc2_$TAG; rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT" -o p -- python3 "$REPO/bench.py" --no-cpu-baseline --steps 4 --warmup 1 > "$OUT/bench.json" 2> "$OUT/stderr.txt"
+rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT" -o p -- python3 "$REPO/bench.py" --full --no-cpu-baseline --steps 4 --warmup 1 > "$OUT/bench.json" 2> "$OUT/stderr.txt"
 python3 - "$OUT" <<'PY'
 import csv, sys, glob, collections, re
 out = sys.argv[1]

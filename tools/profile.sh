@@ -7,6 +7,6 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o bench -- python3 "$REPO/bench.py" --no-cpu-baseline "$@" > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.stderr"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o bench -- python3 "$REPO/bench.py" --full --no-cpu-baseline "$@" > "$OUT/bench_under_rocprof.json" 2> "$OUT/rocprof.stderr"
 echo "rocprofv3 rc=$?"
 find "$OUT" -name "*stats*" | head
