@@ -174,6 +174,28 @@ int tpg_fill_halo_regions_timed(void *const fields[], int nfields,
                                 int Nx, int Ny, int Nz, int Hx, int Hy, int Hz,
                                 int north_is_zipper, int ft, void *stream, void *start_event, void *stop_event);
 
+/* ---- no-flux mirror of the south, bottom and top halos ------------------------------------
+ * Oceananigans' fill of a Flux-class boundary condition (FluxBoundaryCondition / NoFluxBoundaryCondition, which its
+ * HydrostaticFreeSurfaceModel puts on every bounded side where a field is at Center; the reference keeps them and replaces only
+ * the north side, src/tripolar_grid_extensions.jl:25-44, 57-80): a no-flux mirror whatever the flux value [recalled:
+ * fill_halo_regions_flux.jl].  A POST-PASS: call it after the horizontal fill of the same fields (tpg_fill_halo_regions, or
+ * tpg_zipper_fill + tpg_periodic_x_fill, or a whole tpg_fill_halo_regions_distributed* call, or the unpack of a host-driven seam
+ * exchange).  sides[f] is an OR of the TPG_SIDE_* bits of field f; it writes exactly (1-based, padded rows and planes):
+ *     TPG_SIDE_SOUTH   c[i, 1-j, k]  = c[i, j, k]        j = 1..Hy, i = 1-Hx..Nx+Hx, k = 1..Nz
+ *     TPG_SIDE_BOTTOM  c[i, j, 1-k]  = c[i, j, k]        k = 1..Hz, every (i, j) of the padded plane
+ *     TPG_SIDE_TOP     c[i, j, Nz+k] = c[i, j, Nz+1-k]   k = 1..Hz, every (i, j) of the padded plane
+ * i.e. south first, then bottom and top: a south-and-bottom corner c[i, 1-j, 1-k] takes c[i, j, k] (read directly -- no cell is
+ * read after this call has written it).  ONE launch per batch of up to TPG_MAX_FIELDS fields (more are split); Float32 and Float64,
+ * every halo width, every pointer aligned to the element type (16-B chunks, element-aligned where rows are off the 16-B grid).
+ * A side without a halo (Hy = 0, Hz = 0: a field reduced or windowed in z) is a no-op.  The sources must be interior rows / levels
+ * that the horizontal fill does not write: TPG_ERR_UNSUPPORTED for TPG_SIDE_SOUTH with Ny <= Hy and for TPG_SIDE_BOTTOM / _TOP with
+ * Nz < Hz; TPG_ERR_INVALID_ARGUMENT for a sides value with other bits, a null table or a pointer off its element alignment. */
+#define TPG_SIDE_SOUTH 1
+#define TPG_SIDE_BOTTOM 2
+#define TPG_SIDE_TOP 4
+int tpg_fill_bounded_halos(void *const fields[], int nfields, const uint8_t sides[],
+                           int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
+
 /* ---- latitude-band halo exchange helpers (config 4) -------------------------------------
  * The interior seams of a y-slab partition exchange Hy full rows (all i incl. x halos, all
  * levels incl. z halos) per side and field; the transport (RCCL send/recv, ROCm-aware MPI) stays

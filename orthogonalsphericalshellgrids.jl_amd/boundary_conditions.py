@@ -36,6 +36,20 @@ class HaloCommunication(AbstractBoundaryConditionClassification):
         return "HaloCommunication()"
 
 
+class Flux(AbstractBoundaryConditionClassification):
+    """Oceananigans' Flux classification [recalled]: the default of every bounded side where a field is at Center.  Its halo is filled
+    as a no-flux mirror whatever the flux value (the flux enters the tendency, not the halo): tpg_fill_bounded_halos."""
+
+    def __repr__(self):
+        return "Flux()"
+
+    def __eq__(self, other):             # a field-less singleton type in Julia: Flux() == Flux()
+        return isinstance(other, Flux)
+
+    def __hash__(self):
+        return hash(Flux)
+
+
 @dataclass(frozen=True)
 class BoundaryCondition:
     classification: Any
@@ -55,6 +69,20 @@ def HaloCommunicationBoundaryCondition(from_rank, to_rank):
     return BoundaryCondition(HaloCommunication(), (from_rank, to_rank))
 
 
+def FluxBoundaryCondition(condition=None):
+    """FluxBoundaryCondition(condition) = BoundaryCondition(Flux(), condition)   [recalled, Oceananigans]"""
+    return BoundaryCondition(Flux(), condition)
+
+
+def NoFluxBoundaryCondition():
+    """NoFluxBoundaryCondition() = BoundaryCondition(Flux(), nothing)   [recalled, Oceananigans]"""
+    return FluxBoundaryCondition(None)
+
+
+def is_flux(bc):
+    return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Flux)
+
+
 def is_zipper(bc):
     """bc isa ZBC  (const ZBC = BoundaryCondition{<:Zipper}, :54)"""
     return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Zipper)
@@ -68,11 +96,15 @@ def bc_str(bc):
 
 
 def validate_boundary_condition_location(bc, loc, side):
-    """(:58-62) a Zipper classification is valid on the north side only."""
+    """(:58-62) a Zipper classification is valid on the north side only.  A Flux classification is invalid where the field sits at
+    Face on the side's axis (Oceananigans' validate_boundary_condition_location [recalled]: that side's boundary value is the field's own
+    face value, e.g. south on v or zeta, bottom / top on a ZFaceField)."""
     cls = bc.classification if isinstance(bc, BoundaryCondition) else bc
+    name = loc.__name__ if isinstance(loc, type) else type(loc).__name__
     if isinstance(cls, Zipper) and side != "north":
-        name = loc.__name__ if isinstance(loc, type) else type(loc).__name__
         raise ValueError(f"Cannot specify {side} boundary condition {cls!r} on a field at {name} (north only)!")
+    if isinstance(cls, Flux) and loc is Face:
+        raise ValueError(f"Cannot specify {side} boundary condition {cls!r} on a field at {name}!")
     return None
 
 

@@ -5,7 +5,8 @@ the halo-fill entry that reaches _fill_north_halo! (src/zipper_boundary_conditio
 Field data is one torch tensor of shape (Nz'+2Hz, Ny+2Hy, Nx+2Hx) in HBM whose memory is the
 `parent` of the reference's OffsetArray (i fastest).  fill_halo_regions batches every field of
 one geometry into ONE zipper launch + one periodic-x launch, or into a single fused launch when the
-fields are small (tpg_fill_halo_regions).
+fields are small (tpg_fill_halo_regions); fields with no-flux south / bottom / top sides get one more launch after the horizontal
+fill (tpg_fill_bounded_halos).
 """
 import ctypes as C
 
@@ -14,7 +15,7 @@ import torch
 from . import _lib
 from .boundary_conditions import (Center, Face, FieldBoundaryConditions, PeriodicBoundaryCondition,
                                   ZipperBoundaryCondition, HaloCommunicationBoundaryCondition,
-                                  is_zipper, sign)
+                                  is_flux, is_zipper, sign)
 from .grids import is_tripolar
 
 
@@ -172,9 +173,9 @@ def _groups(fields):
 
 def _check_supported(f):
     """Scope of this halo fill: the north Zipper (the reference's own code), Oceananigans' periodic x pass
-    that must follow it, and the latitude-band seams.  South / bottom / top conditions and non-periodic x conditions are
-    Oceananigans' (the reference's own fills leave them `nothing`, src/tripolar_grid.jl:147-152): a field that carries one
-    is refused loudly instead of being returned with stale halos."""
+    that must follow it, the latitude-band seams, and the no-flux mirror of Flux-class south / bottom / top sides (the default
+    conditions of a model's Center fields).  Every other south / bottom / top condition (Value, Gradient, Open) and every
+    non-periodic x condition is Oceananigans': a field that carries one is refused loudly instead of being returned with stale halos."""
     from .boundary_conditions import HaloCommunication, Periodic
     bcs = f.boundary_conditions
     for side in ("west", "east"):
@@ -184,12 +185,26 @@ def _check_supported(f):
                                       "(tripolar grids are Periodic in x)")
     for side in ("south", "north"):
         bc = getattr(bcs, side)
-        if bc is not None and not is_zipper(bc) and not isinstance(bc.classification, HaloCommunication):
+        if bc is not None and not is_zipper(bc) and not isinstance(bc.classification, HaloCommunication) \
+                and not (side == "south" and is_flux(bc)):
             raise NotImplementedError(f"fill_halo_regions: {side} boundary condition {bc.classification!r} is Oceananigans' to fill; "
-                                      "this library fills the Zipper north side, periodic x and the latitude-band seams only")
+                                      "this library fills the Zipper north side, periodic x, the latitude-band seams and no-flux sides only")
     for side in ("bottom", "top"):
-        if getattr(bcs, side) is not None:
-            raise NotImplementedError(f"fill_halo_regions: {side} boundary conditions (z halos) are Oceananigans' to fill, not handled here")
+        bc = getattr(bcs, side)
+        if bc is not None and not is_flux(bc):
+            raise NotImplementedError(f"fill_halo_regions: {side} boundary condition {bc.classification!r} is Oceananigans' to fill; "
+                                      "this library fills no-flux (Flux-class) z halos only")
+
+
+def _sides(fs):
+    """per-field TPG_SIDE_* bits of tpg_fill_bounded_halos (None if no field of the group has one): every Flux-class south, bottom and
+    top side is a no-flux mirror.  A side whose axis has no halo is a no-op in the C call."""
+    bits = []
+    for f in fs:
+        b = f.boundary_conditions
+        bits.append((_lib.TPG_SIDE_SOUTH if is_flux(b.south) else 0) | (_lib.TPG_SIDE_BOTTOM if is_flux(b.bottom) else 0)
+                    | (_lib.TPG_SIDE_TOP if is_flux(b.top) else 0))
+    return (C.c_uint8 * len(fs))(*bits) if any(bits) else None
 
 
 def _tables(fs):
@@ -236,7 +251,9 @@ class HaloFillPlan:
 
     Order (pinned by test/test_zipper_boundary_conditions.jl:42-45):
     zipper fold on the north side (serial grid or last rank) -> periodic x (fills corners) ->
-    on a distributed grid the y-seam exchange of Hy rows with the neighbour ranks.
+    on a distributed grid the y-seam exchange of Hy rows with the neighbour ranks -> the no-flux mirror of Flux-class south
+    (serial grid or rank 0), bottom and top sides (tpg_fill_bounded_halos: one call per geometry group, after the horizontal fill
+    and after the seam exchange has delivered -- in finish() on the host-driven band path).
     `exchange` overrides the transport (used by the CPU/gloo tests of the host logic).
     The plan holds the fields' tensors: it must be rebuilt if a field's `data` is replaced.
     """
@@ -253,6 +270,7 @@ class HaloFillPlan:
         self._comm_streams = {}                               # device -> the second stream of the pipelined RCCL exchange
         self._steps = []                      # (device, [(c function, argument tuple without the stream)], PendingExchange or None)
         self._keep = []                       # message buffers referenced by raw pointer from the argument tuples
+        self._post = []                       # per step: calls that follow the host-driven seam exchange (run by finish())
         lib = _lib.lib()
         for f in self.fields:
             if f.boundary_conditions is not None:
@@ -267,7 +285,11 @@ class HaloFillPlan:
             distributed = getattr(arch, "is_distributed", False) and arch.ranks[1] > 1
             comm = getattr(arch, "rccl_comm", None) if (distributed and exchange is None) else None
             uniform = len(zip_fs) in (0, len(fs))
-            calls, pending = [], None
+            calls, pending, post = [], None, []
+            sides = _sides(fs)
+            # no-flux south / bottom / top: a local post-pass over the whole group, after everything that writes the horizontal halos
+            bounded = None if sides is None else \
+                (lib.tpg_fill_bounded_halos, (_lib.ptr_table([f.data for f in fs]), len(fs), sides, *geom, ft))
             if comm is not None:
                 # EVERY rank of the chain enters the agreement, before it picks its branch: a rank whose fields are not uniformly zipped takes
                 # the host-driven branch below, and its peers must not be left waiting in the collective for it
@@ -294,6 +316,8 @@ class HaloFillPlan:
                                       (C.c_void_p(self._comm_streams[dev].cuda_stream), self._fields_per_stage)))
                     else:
                         calls.append((lib.tpg_fill_halo_regions_distributed, args))
+                if bounded is not None:
+                    calls.append(bounded)        # on the caller's stream, which every batch's call (pipelined: its joined streams) precedes
             else:
                 if zip_fs and len(zip_fs) == len(fs):
                     # the usual case: one entry point for zipper -> periodic x (a single fused launch for small
@@ -309,7 +333,10 @@ class HaloFillPlan:
                 if distributed:
                     from .distributed import PendingExchange
                     pending = PendingExchange(fs, arch, exchange, pack_free, self._fields_per_stage)     # owns its message buffers; reused every fill
+                if bounded is not None:
+                    (post if pending is not None else calls).append(bounded)
             self._steps.append((f0.data.device, calls, pending))
+            self._post.append(post)
 
     @property
     def is_distributed(self):
@@ -319,24 +346,18 @@ class HaloFillPlan:
         """local part of the fill (zipper, periodic x) on every geometry group, then pack + post of the seam exchange
         (on the RCCL path the one C call has done the whole fill, exchange included, by the time begin() returns)"""
         for device, calls, pending in self._steps:
-            if torch.cuda.current_device() == device.index:     # the common case: no device switch to pay for
-                stream = _lib.current_stream_ptr(device)
-                for fn, args, *after in calls:                 # after: arguments that follow the stream (pipelined exchange)
-                    _lib.check(fn(*args, stream, *(after[0] if after else ())))
-            else:
-                with torch.cuda.device(device):
-                    stream = _lib.current_stream_ptr(device)
-                    for fn, args, *after in calls:
-                        _lib.check(fn(*args, stream, *(after[0] if after else ())))
+            _run(device, calls)
             if pending is not None:
                 pending.begin()
         return self
 
     def finish(self):
-        """delivery + unpack of the seam messages posted by begin()"""
-        for _, _, pending in self._steps:
+        """delivery + unpack of the seam messages posted by begin(), then the no-flux mirror of the fields that took them"""
+        for (device, _, pending), post in zip(self._steps, self._post):
             if pending is not None:
                 pending.finish()
+            if post:
+                _run(device, post)
         return None
 
     def __call__(self):
@@ -361,6 +382,19 @@ class HaloFillPlan:
                 self()
         torch.cuda.current_stream().wait_stream(side)
         return g
+
+
+def _run(device, calls):
+    """issue `calls` on torch's current stream of `device`"""
+    if torch.cuda.current_device() == device.index:     # the common case: no device switch to pay for
+        stream = _lib.current_stream_ptr(device)
+        for fn, args, *after in calls:                 # after: arguments that follow the stream (pipelined exchange)
+            _lib.check(fn(*args, stream, *(after[0] if after else ())))
+    else:
+        with torch.cuda.device(device):
+            stream = _lib.current_stream_ptr(device)
+            for fn, args, *after in calls:
+                _lib.check(fn(*args, stream, *(after[0] if after else ())))
 
 
 def halo_fill_plan(fields, *, exchange=None, pack_free=False, fields_per_stage=0):
