@@ -196,6 +196,33 @@ int tpg_fill_halo_regions_timed(void *const fields[], int nfields,
 int tpg_fill_bounded_halos(void *const fields[], int nfields, const uint8_t sides[],
                            int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
 
+/* ---- Value / Gradient south, bottom and top halos -------------------------------------------
+ * Oceananigans' fill of Value- and Gradient-class conditions (ValueBoundaryCondition(v), GradientBoundaryCondition(g)) [recalled:
+ * fill_halo_regions_value_gradient.jl; parity unpinned]: ONLY THE FIRST halo point of a side is written, by a linear extrapolation
+ * from the adjacent interior cell.  1-based, every operation in the field's type FT, in exactly this order (no contraction):
+ *     south   c[i, 0, k]    = c[i, 1, k]  + D * (-d)   d = dy_cf[i, 1]    i = 1-Hx..Nx+Hx, k = 1..Nz
+ *     bottom  c[i, j, 0]    = c[i, j, 1]  + D * (-d)   d = dz_bottom      every (i, j) of the padded plane
+ *     top     c[i, j, Nz+1] = c[i, j, Nz] + D * d      d = dz_top         every (i, j) of the padded plane
+ * with D = (c[1] - v) / (d / 2) for Value (top: (v - c[Nz]) / (d / 2)) and D = g for Gradient, c[1] / c[Nz] the source cell above.
+ * Rows j <= -1 and planes k <= -1, k >= Nz+2 are not touched.  A POST-PASS in two calls around tpg_fill_bounded_halos: after the
+ * horizontal fill (see tpg_fill_bounded_halos) call pass = TPG_SIDE_SOUTH, then tpg_fill_bounded_halos, then pass = TPG_SIDE_BOTTOM
+ * and / or TPG_SIDE_TOP -- south first, then bottom and top, whatever the class of each side.  Sides not in `pass` are skipped.
+ * Per field f and side s (0 south, 1 bottom, 2 top): kinds[3f+s] is 0 (none), TPG_BC_VALUE or TPG_BC_GRADIENT; the condition is
+ * conditions[3f+s], a device array of FT read at call time, or, where that is NULL, values[3f+s] (a double holding an FT value):
+ *     south: (Nz, Nx+2Hx) array, entry [k-1][i+Hx-1];  bottom / top: (Ny+2Hy, Nx+2Hx), entry [j+Hy-1][i+Hx-1].
+ * dy_cf is the padded 2-D metric Dy at (Center, Face) of the fields' grid, (Ny+2Hy, Nx+2Hx) of FT, read in its row j = 1 (needed when
+ * a south kind is set); dz_bottom / dz_top are the z spacings at faces 1 and Nz+1 (FT values).  ONE launch per batch of up to
+ * TPG_MAX_FIELDS fields that have a kind in the pass (more are split); Float32 and Float64, every halo width, every pointer aligned to
+ * the element type.  A side without a halo (Hy = 0, Hz = 0) is a no-op.  Every check precedes any launch: TPG_ERR_INVALID_ARGUMENT
+ * for a pass that is empty, has other bits or mixes TPG_SIDE_SOUTH with bottom / top, a null table, an unknown kind, a south kind
+ * with a null dy_cf, or a pointer off its element alignment; TPG_ERR_UNSUPPORTED for a south kind with Ny < 2 (row 1 is then the
+ * zipper's row Ny) or a launch too large for 32-bit work-item indices. */
+#define TPG_BC_VALUE 1
+#define TPG_BC_GRADIENT 2
+int tpg_fill_value_gradient_halos(void *const fields[], int nfields, int pass, const uint8_t kinds[], const double values[],
+                                  const void *const conditions[], const void *dy_cf, double dz_bottom, double dz_top,
+                                  int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
+
 /* ---- latitude-band halo exchange helpers (config 4) -------------------------------------
  * The interior seams of a y-slab partition exchange Hy full rows (all i incl. x halos, all
  * levels incl. z halos) per side and field; the transport (RCCL send/recv, ROCm-aware MPI) stays

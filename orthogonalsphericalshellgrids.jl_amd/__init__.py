@@ -9,8 +9,10 @@ All numerics run in hand-written HIP kernels (csrc/, C ABI in include/tripolar_h
 from .boundary_conditions import (BoundaryCondition, Center, Face, FieldBoundaryConditions, Zipper,
                                   ZipperBoundaryCondition, PeriodicBoundaryCondition, bc_str,
                                   Flux, FluxBoundaryCondition, NoFluxBoundaryCondition,
+                                  Value, ValueBoundaryCondition, Gradient, GradientBoundaryCondition,
                                   apply_y_north_bc, regularize_field_boundary_conditions, sign,
-                                  validate_boundary_condition_location, is_flux, is_zipper)
+                                  validate_boundary_condition_location, is_flux, is_gradient, is_value,
+                                  is_zipper)
 from .grids import (CPU, GPU, convert_to_0_360, Distributed, Partition, OrthogonalSphericalShellGrid, R_Earth, Tripolar,
                     TripolarGrid, is_tripolar, local_row_range, local_sizes, reconstruct_global_grid, share_tables,
                     with_halo, x_domain, y_domain, RightConnected, FullyConnected, Bounded,

@@ -13,6 +13,7 @@ TPG_F32, TPG_F64 = 0, 1
 TPG_CENTER, TPG_FACE = 0, 1
 TPG_MAX_FIELDS = 16
 TPG_SIDE_SOUTH, TPG_SIDE_BOTTOM, TPG_SIDE_TOP = 1, 2, 4      # tpg_fill_bounded_halos side bits
+TPG_BC_VALUE, TPG_BC_GRADIENT = 1, 2                         # tpg_fill_value_gradient_halos kinds
 TPG_BUILD_TABLES_VALID = 1        # tpg_params.reserved flag
 
 # enum tpg_array (order of src/tripolar_grid.jl:308-328 in the reference)
@@ -72,6 +73,8 @@ SIGNATURES = {
     "tpg_fill_halo_regions_timed": (_i, [C.POINTER(_vp), _i, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.POINTER(C.c_int32)]
                                     + _geom + [_i, _i, _vp, _vp, _vp]),
     "tpg_fill_bounded_halos": (_i, [C.POINTER(_vp), _i, C.POINTER(C.c_uint8)] + _geom + [_i, _vp]),
+    "tpg_fill_value_gradient_halos": (_i, [C.POINTER(_vp), _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(_vp), _vp,
+                                           C.c_double, C.c_double] + _geom + [_i, _vp]),
     "tpg_y_halo_buffer_elems": (_sz, [_i] * 6),
     "tpg_pack_y_halo": (_i, [C.POINTER(_vp), _i, _vp, _i] + _geom + [_i, _vp]),
     "tpg_unpack_y_halo": (_i, [C.POINTER(_vp), _i, _vp, _i] + _geom + [_i, _vp]),

@@ -50,6 +50,34 @@ class Flux(AbstractBoundaryConditionClassification):
         return hash(Flux)
 
 
+class Value(AbstractBoundaryConditionClassification):
+    """Oceananigans' Value classification [recalled]: a prescribed boundary value v.  Only the first halo point is written, extrapolated
+    linearly from the adjacent interior cell through v at the boundary face: tpg_fill_value_gradient_halos."""
+
+    def __repr__(self):
+        return "Value()"
+
+    def __eq__(self, other):             # a field-less singleton type in Julia: Value() == Value()
+        return isinstance(other, Value)
+
+    def __hash__(self):
+        return hash(Value)
+
+
+class Gradient(AbstractBoundaryConditionClassification):
+    """Oceananigans' Gradient classification [recalled]: a prescribed normal gradient g at the boundary face.  Only the first halo point is
+    written, c⁰ = c¹ ∓ g Δ: tpg_fill_value_gradient_halos."""
+
+    def __repr__(self):
+        return "Gradient()"
+
+    def __eq__(self, other):
+        return isinstance(other, Gradient)
+
+    def __hash__(self):
+        return hash(Gradient)
+
+
 @dataclass(frozen=True)
 class BoundaryCondition:
     classification: Any
@@ -79,8 +107,27 @@ def NoFluxBoundaryCondition():
     return FluxBoundaryCondition(None)
 
 
+def ValueBoundaryCondition(condition):
+    """ValueBoundaryCondition(condition) = BoundaryCondition(Value(), condition)   [recalled, Oceananigans]"""
+    return BoundaryCondition(Value(), condition)
+
+
+def GradientBoundaryCondition(condition):
+    """GradientBoundaryCondition(condition) = BoundaryCondition(Gradient(), condition)   [recalled, Oceananigans]"""
+    return BoundaryCondition(Gradient(), condition)
+
+
 def is_flux(bc):
     return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Flux)
+
+
+def is_value(bc):
+    """the library's own Value classification (isinstance: another class that happens to be named Value is not it)"""
+    return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Value)
+
+
+def is_gradient(bc):
+    return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Gradient)
 
 
 def is_zipper(bc):
@@ -96,14 +143,14 @@ def bc_str(bc):
 
 
 def validate_boundary_condition_location(bc, loc, side):
-    """(:58-62) a Zipper classification is valid on the north side only.  A Flux classification is invalid where the field sits at
-    Face on the side's axis (Oceananigans' validate_boundary_condition_location [recalled]: that side's boundary value is the field's own
-    face value, e.g. south on v or zeta, bottom / top on a ZFaceField)."""
+    """(:58-62) a Zipper classification is valid on the north side only.  A Flux, Value or Gradient classification is invalid where the
+    field sits at Face on the side's axis (Oceananigans' validate_boundary_condition_location [recalled]: that side's boundary value is the
+    field's own face value, e.g. south on v or zeta, bottom / top on a ZFaceField)."""
     cls = bc.classification if isinstance(bc, BoundaryCondition) else bc
     name = loc.__name__ if isinstance(loc, type) else type(loc).__name__
     if isinstance(cls, Zipper) and side != "north":
         raise ValueError(f"Cannot specify {side} boundary condition {cls!r} on a field at {name} (north only)!")
-    if isinstance(cls, Flux) and loc is Face:
+    if isinstance(cls, (Flux, Value, Gradient)) and loc is Face:
         raise ValueError(f"Cannot specify {side} boundary condition {cls!r} on a field at {name}!")
     return None
 

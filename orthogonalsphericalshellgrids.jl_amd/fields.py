@@ -6,17 +6,19 @@ Field data is one torch tensor of shape (Nz'+2Hz, Ny+2Hy, Nx+2Hx) in HBM whose m
 `parent` of the reference's OffsetArray (i fastest).  fill_halo_regions batches every field of
 one geometry into ONE zipper launch + one periodic-x launch, or into a single fused launch when the
 fields are small (tpg_fill_halo_regions); fields with no-flux south / bottom / top sides get one more launch after the horizontal
-fill (tpg_fill_bounded_halos).
+fill (tpg_fill_bounded_halos); fields with Value / Gradient south / bottom / top sides get one launch before that mirror (south) and one after
+it (bottom / top): tpg_fill_value_gradient_halos.
 """
 import ctypes as C
+import numbers
 
 import torch
 
 from . import _lib
 from .boundary_conditions import (Center, Face, FieldBoundaryConditions, PeriodicBoundaryCondition,
                                   ZipperBoundaryCondition, HaloCommunicationBoundaryCondition,
-                                  is_flux, is_zipper, sign)
-from .grids import is_tripolar
+                                  is_flux, is_gradient, is_value, is_zipper, sign)
+from .grids import boundary_z_spacings, is_tripolar
 
 
 def _loc_code(L):
@@ -173,9 +175,10 @@ def _groups(fields):
 
 def _check_supported(f):
     """Scope of this halo fill: the north Zipper (the reference's own code), Oceananigans' periodic x pass
-    that must follow it, the latitude-band seams, and the no-flux mirror of Flux-class south / bottom / top sides (the default
-    conditions of a model's Center fields).  Every other south / bottom / top condition (Value, Gradient, Open) and every
-    non-periodic x condition is Oceananigans': a field that carries one is refused loudly instead of being returned with stale halos."""
+    that must follow it, the latitude-band seams, the no-flux mirror of Flux-class south / bottom / top sides (the default
+    conditions of a model's Center fields) and the first-halo-point extrapolation of Value / Gradient south / bottom / top sides.  Every
+    other south / bottom / top condition (Open, unknown classes) and every non-periodic x condition is Oceananigans': a field that carries
+    one is refused loudly instead of being returned with stale halos."""
     from .boundary_conditions import HaloCommunication, Periodic
     bcs = f.boundary_conditions
     for side in ("west", "east"):
@@ -186,14 +189,19 @@ def _check_supported(f):
     for side in ("south", "north"):
         bc = getattr(bcs, side)
         if bc is not None and not is_zipper(bc) and not isinstance(bc.classification, HaloCommunication) \
-                and not (side == "south" and is_flux(bc)):
+                and not (side == "south" and _bounded_class(bc)):
             raise NotImplementedError(f"fill_halo_regions: {side} boundary condition {bc.classification!r} is Oceananigans' to fill; "
-                                      "this library fills the Zipper north side, periodic x, the latitude-band seams and no-flux sides only")
+                                      "this library fills the Zipper north side, periodic x, the latitude-band seams and Flux, Value "
+                                      "and Gradient sides only")
     for side in ("bottom", "top"):
         bc = getattr(bcs, side)
-        if bc is not None and not is_flux(bc):
+        if bc is not None and not _bounded_class(bc):
             raise NotImplementedError(f"fill_halo_regions: {side} boundary condition {bc.classification!r} is Oceananigans' to fill; "
-                                      "this library fills no-flux (Flux-class) z halos only")
+                                      "this library fills Flux, Value and Gradient z halos only")
+
+
+def _bounded_class(bc):
+    return is_flux(bc) or is_value(bc) or is_gradient(bc)
 
 
 def _sides(fs):
@@ -205,6 +213,71 @@ def _sides(fs):
         bits.append((_lib.TPG_SIDE_SOUTH if is_flux(b.south) else 0) | (_lib.TPG_SIDE_BOTTOM if is_flux(b.bottom) else 0)
                     | (_lib.TPG_SIDE_TOP if is_flux(b.top) else 0))
     return (C.c_uint8 * len(fs))(*bits) if any(bits) else None
+
+
+_VG_SIDES = ("south", "bottom", "top")        # the side order of tpg_fill_value_gradient_halos' 3-per-field tables
+
+
+def _condition(f, side, bc):
+    """(value, pointer, tensor) that tpg_fill_value_gradient_halos takes for one Value / Gradient side of field f: a number or a 0-d tensor is
+    rounded once to the field's type here (value; pointer None); a device array -- south (Nz, Nx+2Hx), bottom / top (Ny+2Hy, Nx+2Hx), or a
+    reduced Field((LX, LY, None)) on the same grid as a bottom / top condition -- is read at call time (pointer; the plan holds the tensor).
+    Anything else raises ValueError, with the expected shape."""
+    dtype, device = f.data.dtype, f.data.device
+    sx = f.Nx + 2 * f.Hx
+    shape = (f.Nz, sx) if side == "south" else (f.Ny + 2 * f.Hy, sx)
+    want = (f"a number, a 0-d tensor or a contiguous {shape} tensor of {dtype} on {device}"
+            + ("" if side == "south" else f", or a reduced Field(({f.loc[0].__name__}, {f.loc[1].__name__}, None)) on the same grid"))
+    c = bc.condition
+    if isinstance(c, Field):
+        if side == "south" or c.loc != (f.loc[0], f.loc[1], None) or c.grid is not f.grid:
+            raise ValueError(f"fill_halo_regions: {side} {bc.classification!r} condition {c!r} is not {want}")
+        c = c.data.view(c.data.shape[-2:])                   # its data: (1, Ny+2Hy, Nx+2Hx), halos the caller's
+    if isinstance(c, numbers.Real) and not isinstance(c, bool):
+        return torch.tensor(c, dtype=dtype).item(), None, None
+    if torch.is_tensor(c) and c.dim() == 0:
+        return c.detach().cpu().to(dtype).item(), None, None
+    if torch.is_tensor(c) and tuple(c.shape) == shape and c.is_contiguous() and c.device == device and c.dtype == dtype:
+        return 0.0, c.data_ptr(), c
+    got = f"a {tuple(c.shape)} tensor of {c.dtype} on {c.device}" if torch.is_tensor(c) else repr(c)
+    raise ValueError(f"fill_halo_regions: {side} {bc.classification!r} condition must be {want}; got {got}"
+                     + (" (function-valued conditions need Oceananigans' clock)" if callable(c) else ""))
+
+
+def _value_gradient_calls(lib, fs, geom, ft, held):
+    """(south call, bottom / top call) of tpg_fill_value_gradient_halos for one geometry group, None where no field has such a side; the
+    tensors the calls read by pointer go to `held`.  The south spacing is dy_cf (Dy at (Center, Face), row j = 1) for every field location
+    [recalled: Oceananigans' Dy(i, 1, k) at (c, f, c)]; the z spacings come from the grid's z_spec, computed for a group with a z side only."""
+    n = len(fs)
+    kinds, values, conds = [0] * (3 * n), [0.0] * (3 * n), [None] * (3 * n)
+    for fi, f in enumerate(fs):
+        for s, side in enumerate(_VG_SIDES):
+            bc = getattr(f.boundary_conditions, side)
+            if is_value(bc) or is_gradient(bc):
+                kinds[3 * fi + s] = _lib.TPG_BC_VALUE if is_value(bc) else _lib.TPG_BC_GRADIENT
+                values[3 * fi + s], conds[3 * fi + s], t = _condition(f, side, bc)
+                if t is not None:
+                    held.append(t)
+    south = any(kinds[0::3])
+    zpass = (_lib.TPG_SIDE_BOTTOM if any(kinds[1::3]) else 0) | (_lib.TPG_SIDE_TOP if any(kinds[2::3]) else 0)
+    if not (south or zpass):
+        return None, None
+    f0 = fs[0]
+    g = getattr(f0.grid, "underlying_grid", f0.grid)
+    dy = None
+    if south:
+        dy = g.arrays["dy_cf"]
+        if dy.dtype != f0.data.dtype or dy.device != f0.data.device:
+            dy = dy.to(device=f0.data.device, dtype=f0.data.dtype)
+        dy = dy.contiguous()
+        held.append(dy)
+    dzb, dzt = boundary_z_spacings(g, f0.data.dtype) if zpass else (0.0, 0.0)
+    ptrs = _lib.ptr_table([f.data for f in fs])
+    tail = ((C.c_uint8 * (3 * n))(*kinds), (C.c_double * (3 * n))(*values), (C.c_void_p * (3 * n))(*conds),
+            None if dy is None else C.c_void_p(dy.data_ptr()), dzb, dzt, *geom, ft)
+    fn = lib.tpg_fill_value_gradient_halos
+    return ((fn, (ptrs, n, _lib.TPG_SIDE_SOUTH, *tail)) if south else None,
+            (fn, (ptrs, n, zpass, *tail)) if zpass else None)
 
 
 def _tables(fs):
@@ -253,7 +326,8 @@ class HaloFillPlan:
     zipper fold on the north side (serial grid or last rank) -> periodic x (fills corners) ->
     on a distributed grid the y-seam exchange of Hy rows with the neighbour ranks -> the no-flux mirror of Flux-class south
     (serial grid or rank 0), bottom and top sides (tpg_fill_bounded_halos: one call per geometry group, after the horizontal fill
-    and after the seam exchange has delivered -- in finish() on the host-driven band path).
+    and after the seam exchange has delivered -- in finish() on the host-driven band path), preceded by the Value / Gradient south pass
+    and followed by the Value / Gradient bottom / top pass (tpg_fill_value_gradient_halos), where a group has such sides.
     `exchange` overrides the transport (used by the CPU/gloo tests of the host logic).
     The plan holds the fields' tensors: it must be rebuilt if a field's `data` is replaced.
     """
@@ -271,6 +345,7 @@ class HaloFillPlan:
         self._steps = []                      # (device, [(c function, argument tuple without the stream)], PendingExchange or None)
         self._keep = []                       # message buffers referenced by raw pointer from the argument tuples
         self._post = []                       # per step: calls that follow the host-driven seam exchange (run by finish())
+        self._held = []                       # Value / Gradient condition arrays and metrics, read by pointer at call time
         lib = _lib.lib()
         for f in self.fields:
             if f.boundary_conditions is not None:
@@ -290,6 +365,9 @@ class HaloFillPlan:
             # no-flux south / bottom / top: a local post-pass over the whole group, after everything that writes the horizontal halos
             bounded = None if sides is None else \
                 (lib.tpg_fill_bounded_halos, (_lib.ptr_table([f.data for f in fs]), len(fs), sides, *geom, ft))
+            # Value / Gradient: south before the mirror, bottom / top after it (the order the fill is defined by)
+            vg_south, vg_z = _value_gradient_calls(lib, fs, geom, ft, self._held)
+            post_pass = [c for c in (vg_south, bounded, vg_z) if c is not None]
             if comm is not None:
                 # EVERY rank of the chain enters the agreement, before it picks its branch: a rank whose fields are not uniformly zipped takes
                 # the host-driven branch below, and its peers must not be left waiting in the collective for it
@@ -316,8 +394,7 @@ class HaloFillPlan:
                                       (C.c_void_p(self._comm_streams[dev].cuda_stream), self._fields_per_stage)))
                     else:
                         calls.append((lib.tpg_fill_halo_regions_distributed, args))
-                if bounded is not None:
-                    calls.append(bounded)        # on the caller's stream, which every batch's call (pipelined: its joined streams) precedes
+                calls.extend(post_pass)          # on the caller's stream, which every batch's call (pipelined: its joined streams) precedes
             else:
                 if zip_fs and len(zip_fs) == len(fs):
                     # the usual case: one entry point for zipper -> periodic x (a single fused launch for small
@@ -333,8 +410,7 @@ class HaloFillPlan:
                 if distributed:
                     from .distributed import PendingExchange
                     pending = PendingExchange(fs, arch, exchange, pack_free, self._fields_per_stage)     # owns its message buffers; reused every fill
-                if bounded is not None:
-                    (post if pending is not None else calls).append(bounded)
+                (post if pending is not None else calls).extend(post_pass)
             self._steps.append((f0.data.device, calls, pending))
             self._post.append(post)
 

@@ -229,6 +229,23 @@ def _z_coordinate(z, Nz, Hz, dtype, device):
     return float(Lz), faces.to(dtype).to(device), centers.to(dtype).to(device)
 
 
+def boundary_z_spacings(grid, dtype=None):
+    """(Δzᵃᵃᶠ[1], Δzᵃᵃᶠ[Nz+1]): the z spacings at the bottom and top faces, the distances between the centres on either side of each
+    (Oceananigans' Δzᵃᵃᶠ [recalled]), computed in float64 from grid.z_spec and rounded ONCE to `dtype` (default: the grid's), returned as
+    Python floats.  A regular interval (z0, z1) gives (z1 - z0) / Nz at both; explicit faces give the float64 difference of the adjacent
+    float64 centres, the halo centre from the faces extrapolated as in _z_coordinate."""
+    Nz = grid.Nz
+    zz = grid.z_spec.flatten().tolist() if torch.is_tensor(grid.z_spec) else list(grid.z_spec)
+    if len(zz) == 2:
+        dz = (float(zz[1]) - float(zz[0])) / Nz
+        bottom = top = dz
+    else:
+        _, _, c = _z_coordinate(zz, Nz, 1, torch.float64, "cpu")          # centres k = 0 .. Nz+1 (one halo level on each side)
+        bottom, top = float(c[1] - c[0]), float(c[Nz + 1] - c[Nz])
+    dt = dtype or grid.dtype
+    return tuple(torch.tensor(d, dtype=torch.float64).to(dt).item() for d in (bottom, top))
+
+
 def local_sizes(N, R, sizes=None):
     """Rows per rank of a y-slab partition (Oceananigans local_size / concatenate_local_sizes,
     src/distributed_tripolar_grid.jl:41-44) [recalled for Equal(): N/R each; the remainder rule is
