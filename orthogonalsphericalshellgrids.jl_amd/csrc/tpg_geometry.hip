@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void k_convert_frame(const T* __restrict__ phi
 // element-aligned, for an Hx that is not a multiple of W -- the reference's model halo (5, 5, 5), examples/bickley_jet.jl:21 -- or
 // 16-B-misaligned arrays (the halo-fill kernels' GEN form does the same: csrc/tpg_zipper_kernels.hpp).
 // Threads are numbered over (chunk, row) jointly: a row of 3600 columns is 1800 chunks = 7.03 blocks of 256, and a grid with one block
-// row per grid row would leave every eighth block with 8 live lanes (round 5, tools/frame_ab.py: -3 .. -5 % with the flat numbering;
+// row per grid row would leave every eighth block with 8 live lanes (round 5, profiles/r05/frame_ab.txt: -3 .. -5 % with the flat numbering;
 // more loads in flight, plain loads, 8 / 32 / all levels per thread: all within +-2 %).
 template <typename T, int W, bool LOOSE>
 __global__ __launch_bounds__(256) void k_convert_frame_vec(const T* __restrict__ phi_cf, const T* __restrict__ phi_fc,
