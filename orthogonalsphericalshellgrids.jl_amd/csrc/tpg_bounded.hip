@@ -16,7 +16,7 @@
 // (the project's name for element-aligned 16-B accesses, tpg_zipper_kernels.hpp) serves every other geometry: Float32 rows of
 // Nx + 2 Hx = 2 mod 4 elements (3610 at the reference's model halo (5, 5, 5)) and element-aligned bases.  In the GEN form the last chunk of
 // a row is moved back to end at the row's end and overlaps its neighbour: both write the same values (no source is written here).
-#include "tpg_zipper_kernels.hpp"
+#include "tpg_launch.hpp"
 
 namespace {
 
@@ -67,14 +67,6 @@ __global__ __launch_bounds__(256) void k_bounded_mirror(BoundedTable t, BoundedA
     *reinterpret_cast<cvec_t*>(c + a.plane * pd + (long long)a.sx * jd + e0) = v;
 }
 
-template <typename T>
-void bounded_launch(dim3 grid, hipStream_t s, const BoundedTable& t, const BoundedArgs& a, int W, bool gen)
-{
-    if (!gen)        hipLaunchKernelGGL((k_bounded_mirror<T, 16 / sizeof(T), false>), grid, dim3(256), 0, s, t, a);
-    else if (W == 2) hipLaunchKernelGGL((k_bounded_mirror<T, 2, true>), grid, dim3(256), 0, s, t, a);
-    else             hipLaunchKernelGGL((k_bounded_mirror<T, 16 / sizeof(T), true>), grid, dim3(256), 0, s, t, a);
-}
-
 }  // namespace
 
 extern "C" {
@@ -82,9 +74,8 @@ extern "C" {
 int tpg_fill_bounded_halos(void* const fields[], int nfields, const uint8_t sides[],
                            int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
-    int rc = tpg::check_geom(Nx, Ny, Nz, Hx, Hy, Hz, ft);
+    int rc = check_call(fields, nfields, Nx, Ny, Nz, Hx, Hy, Hz, ft);
     if (rc) return rc;
-    if ((rc = check_fields(fields, nfields))) return rc;
     if (!sides) { tpg::set_error("null sides table"); return TPG_ERR_INVALID_ARGUMENT; }
     const size_t esz = ft == TPG_F64 ? 8 : 4;
     const int all = TPG_SIDE_SOUTH | TPG_SIDE_BOTTOM | TPG_SIDE_TOP;
@@ -109,8 +100,7 @@ int tpg_fill_bounded_halos(void* const fields[], int nfields, const uint8_t side
     Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     // plain 16-B chunks where every row starts on the 16-B grid, element-aligned 16-B (or, for rows shorter than 16 B, 8-B) chunks otherwise
     const int WMAX = (int)(16 / esz);
-    bool plain = ((size_t)g.sx * esz) % 16 == 0;
-    for (int f = 0; f < nfields && plain; ++f) plain = ((uintptr_t)fields[f] % 16) == 0;
+    const bool plain = rows_on_16B_grid((size_t)g.sx * esz, fields, nfields);
     const int W = plain || g.sx >= WMAX ? WMAX : 2;
     BoundedArgs a{ g.sx, g.sy, Nz, Hy, Hz, plain ? g.sx / W : (g.sx + W - 1) / W, g.plane };
     const long long max_rows = 2ll * Hz * g.sy + (long long)Nz * Hy;
@@ -119,8 +109,7 @@ int tpg_fill_bounded_halos(void* const fields[], int nfields, const uint8_t side
         return TPG_ERR_UNSUPPORTED;
     }
     hipStream_t s = tpg::as_stream(stream);
-    for (int f0 = 0; f0 < nfields; f0 += TPG_MAX_FIELDS) {
-        const int n = nfields - f0 < TPG_MAX_FIELDS ? nfields - f0 : TPG_MAX_FIELDS;
+    return for_each_batch(nfields, [&](int f0, int n) {
         BoundedTable t;
         long long rows = 0;
         for (int f = 0; f < n; ++f) {
@@ -130,13 +119,15 @@ int tpg_fill_bounded_halos(void* const fields[], int nfields, const uint8_t side
                                + ((t.sides[f] & TPG_SIDE_SOUTH) ? (long long)Nz * Hy : 0);
             rows = rf > rows ? rf : rows;
         }
-        if (rows == 0) continue;
+        if (rows == 0) return (int)TPG_OK;
         dim3 grid((unsigned)((rows * a.cpr + 255) / 256), (unsigned)n);
-        if (ft == TPG_F64) bounded_launch<double>(grid, s, t, a, W, !plain);
-        else               bounded_launch<float>(grid, s, t, a, W, !plain);
-        if ((rc = tpg::launch_status("k_bounded_mirror"))) return rc;
-    }
-    return TPG_OK;
+        dispatch_ft(ft, [&](auto ty) {
+            dispatch_chunk<decltype(ty)>(W, !plain, [&](auto w, auto gen) {
+                hipLaunchKernelGGL((k_bounded_mirror<decltype(ty), decltype(w)::value, decltype(gen)::value>), grid, dim3(256), 0, s, t, a);
+            });
+        });
+        return tpg::launch_status("k_bounded_mirror");
+    });
 }
 
 }  // extern "C"

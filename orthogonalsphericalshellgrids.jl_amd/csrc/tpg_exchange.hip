@@ -194,6 +194,29 @@ static int exchange_checks(void* comm, int south_peer, int north_peer, void* con
     return TPG_OK;
 }
 
+// a y-slab chain: rank 0 is the southernmost band, rank nranks-1 owns the zipper -- neither of those two sides communicates
+struct Peers { int south, north, north_is_zipper; };
+static int peers_of(int rank, int nranks, Peers* p)
+{
+    if (nranks < 1 || rank < 0 || rank >= nranks) { tpg::set_error("rank %d outside 0:%d", rank, nranks - 1); return TPG_ERR_BAD_PARTITION; }
+    *p = Peers{ rank > 0 ? rank - 1 : -1, rank < nranks - 1 ? rank + 1 : -1, rank == nranks - 1 };
+    return TPG_OK;
+}
+
+// what the two whole distributed fills check before the local fill
+static int distributed_fill_checks(int south_peer, int north_peer, int north_is_zipper, int nfields)
+{
+    if (north_is_zipper && north_peer >= 0) {
+        tpg::set_error("the north side is either the zipper or a seam, not both (north_peer %d)", north_peer);
+        return TPG_ERR_INVALID_ARGUMENT;
+    }
+    if (nfields > TPG_MAX_FIELDS && (south_peer >= 0 || north_peer >= 0)) {
+        tpg::set_error("at most %d fields per distributed fill (one seam message per side)", TPG_MAX_FIELDS);
+        return TPG_ERR_UNSUPPORTED;
+    }
+    return TPG_OK;
+}
+
 int tpg_halo_exchange_y_peers(void* comm, int south_peer, int north_peer, void* const fields[], int nfields,
                               void* send_south, void* send_north, void* recv_south, void* recv_north,
                               int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
@@ -360,8 +383,8 @@ int tpg_halo_exchange_y_pipelined(void* comm, int rank, int nranks, void* const 
                                   int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft,
                                   void* stream, void* comm_stream, int fields_per_stage)
 {
-    if (nranks < 1 || rank < 0 || rank >= nranks) { tpg::set_error("rank %d outside 0:%d", rank, nranks - 1); return TPG_ERR_BAD_PARTITION; }
-    return tpg_halo_exchange_y_pipelined_peers(comm, rank > 0 ? rank - 1 : -1, rank < nranks - 1 ? rank + 1 : -1, fields, nfields,
+    Peers p;  if (int rc = peers_of(rank, nranks, &p)) return rc;
+    return tpg_halo_exchange_y_pipelined_peers(comm, p.south, p.north, fields, nfields,
                                                send_south, send_north, recv_south, recv_north, Nx, Ny, Nz, Hx, Hy, Hz, ft,
                                                stream, comm_stream, fields_per_stage);
 }
@@ -370,9 +393,8 @@ int tpg_halo_exchange_y(void* comm, int rank, int nranks, void* const fields[], 
                         void* send_south, void* send_north, void* recv_south, void* recv_north,
                         int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
-    if (nranks < 1 || rank < 0 || rank >= nranks) { tpg::set_error("rank %d outside 0:%d", rank, nranks - 1); return TPG_ERR_BAD_PARTITION; }
-    // rank 0 is the southernmost band, rank nranks-1 owns the zipper: neither of those two sides communicates
-    return tpg_halo_exchange_y_peers(comm, rank > 0 ? rank - 1 : -1, rank < nranks - 1 ? rank + 1 : -1, fields, nfields,
+    Peers p;  if (int rc = peers_of(rank, nranks, &p)) return rc;
+    return tpg_halo_exchange_y_peers(comm, p.south, p.north, fields, nfields,
                                      send_south, send_north, recv_south, recv_north, Nx, Ny, Nz, Hx, Hy, Hz, ft, stream);
 }
 
@@ -386,16 +408,8 @@ int tpg_fill_halo_regions_distributed_peers(void* comm, int south_peer, int nort
                                             void* send_south, void* send_north, void* recv_south, void* recv_north,
                                             int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
-    if (north_is_zipper && north_peer >= 0) {
-        tpg::set_error("the north side is either the zipper or a seam, not both (north_peer %d)", north_peer);
-        return TPG_ERR_INVALID_ARGUMENT;
-    }
-    if (nfields > TPG_MAX_FIELDS && (south_peer >= 0 || north_peer >= 0)) {
-        tpg::set_error("at most %d fields per distributed fill (one seam message per side)", TPG_MAX_FIELDS);
-        return TPG_ERR_UNSUPPORTED;
-    }
-    int rc = tpg_fill_halo_regions(fields, nfields, xloc, yloc, sign, Nx, Ny, Nz, Hx, Hy, Hz, north_is_zipper ? 1 : 0, ft, stream);
-    if (rc) return rc;
+    int rc = distributed_fill_checks(south_peer, north_peer, north_is_zipper, nfields);
+    if (rc || (rc = tpg_fill_halo_regions(fields, nfields, xloc, yloc, sign, Nx, Ny, Nz, Hx, Hy, Hz, north_is_zipper ? 1 : 0, ft, stream))) return rc;
     if (south_peer < 0 && north_peer < 0) return TPG_OK;           // a one-band chain: the serial fill
     return tpg_halo_exchange_y_peers(comm, south_peer, north_peer, fields, nfields, send_south, send_north, recv_south, recv_north,
                                      Nx, Ny, Nz, Hx, Hy, Hz, ft, stream);
@@ -406,8 +420,8 @@ int tpg_fill_halo_regions_distributed(void* comm, int rank, int nranks, void* co
                                       void* send_south, void* send_north, void* recv_south, void* recv_north,
                                       int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
-    if (nranks < 1 || rank < 0 || rank >= nranks) { tpg::set_error("rank %d outside 0:%d", rank, nranks - 1); return TPG_ERR_BAD_PARTITION; }
-    return tpg_fill_halo_regions_distributed_peers(comm, rank > 0 ? rank - 1 : -1, rank < nranks - 1 ? rank + 1 : -1, rank == nranks - 1,
+    Peers p;  if (int rc = peers_of(rank, nranks, &p)) return rc;
+    return tpg_fill_halo_regions_distributed_peers(comm, p.south, p.north, p.north_is_zipper,
                                                    fields, nfields, xloc, yloc, sign, send_south, send_north, recv_south, recv_north,
                                                    Nx, Ny, Nz, Hx, Hy, Hz, ft, stream);
 }
@@ -421,16 +435,8 @@ int tpg_fill_halo_regions_distributed_pipelined_peers(void* comm, int south_peer
                                                       int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft,
                                                       void* stream, void* comm_stream, int fields_per_stage)
 {
-    if (north_is_zipper && north_peer >= 0) {
-        tpg::set_error("the north side is either the zipper or a seam, not both (north_peer %d)", north_peer);
-        return TPG_ERR_INVALID_ARGUMENT;
-    }
-    if (nfields > TPG_MAX_FIELDS && (south_peer >= 0 || north_peer >= 0)) {
-        tpg::set_error("at most %d fields per distributed fill (one seam message per side)", TPG_MAX_FIELDS);
-        return TPG_ERR_UNSUPPORTED;
-    }
-    int rc = tpg_fill_halo_regions(fields, nfields, xloc, yloc, sign, Nx, Ny, Nz, Hx, Hy, Hz, north_is_zipper ? 1 : 0, ft, stream);
-    if (rc) return rc;
+    int rc = distributed_fill_checks(south_peer, north_peer, north_is_zipper, nfields);
+    if (rc || (rc = tpg_fill_halo_regions(fields, nfields, xloc, yloc, sign, Nx, Ny, Nz, Hx, Hy, Hz, north_is_zipper ? 1 : 0, ft, stream))) return rc;
     if (south_peer < 0 && north_peer < 0) return TPG_OK;
     return tpg_halo_exchange_y_pipelined_peers(comm, south_peer, north_peer, fields, nfields, send_south, send_north, recv_south, recv_north,
                                                Nx, Ny, Nz, Hx, Hy, Hz, ft, stream, comm_stream, fields_per_stage);
@@ -442,8 +448,8 @@ int tpg_fill_halo_regions_distributed_pipelined(void* comm, int rank, int nranks
                                                 int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft,
                                                 void* stream, void* comm_stream, int fields_per_stage)
 {
-    if (nranks < 1 || rank < 0 || rank >= nranks) { tpg::set_error("rank %d outside 0:%d", rank, nranks - 1); return TPG_ERR_BAD_PARTITION; }
-    return tpg_fill_halo_regions_distributed_pipelined_peers(comm, rank > 0 ? rank - 1 : -1, rank < nranks - 1 ? rank + 1 : -1, rank == nranks - 1,
+    Peers p;  if (int rc = peers_of(rank, nranks, &p)) return rc;
+    return tpg_fill_halo_regions_distributed_pipelined_peers(comm, p.south, p.north, p.north_is_zipper,
                                                              fields, nfields, xloc, yloc, sign, send_south, send_north, recv_south, recv_north,
                                                              Nx, Ny, Nz, Hx, Hy, Hz, ft, stream, comm_stream, fields_per_stage);
 }

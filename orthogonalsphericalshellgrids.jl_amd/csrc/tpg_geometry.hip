@@ -9,8 +9,7 @@
 //    the geographic frame, from phi differences and the cell metrics.
 // Elementwise, HBM-bound (24 B and 2 x 3 x s B per cell); same deterministic Float64 functions as the metric
 // kernels (tpg_math.hpp), so results are bit-identical to the CPU restatement's (tests/).
-#include "tpg_common.hpp"
-#include <type_traits>
+#include "tpg_launch.hpp"
 #include "tpg_math.hpp"
 
 using namespace tpgm;
@@ -191,10 +190,11 @@ int tpg_nonorthogonality_angle(const void* lambda_ff, const void* phi_ff, const 
     if ((Ny + NR - 2) / (NR - 1) > 65535) { tpg::set_error("Ny too large"); return TPG_ERR_UNSUPPORTED; }
     dim3 grid((Nx + 62) / 63, (Ny + NR - 2) / (NR - 1));
     hipStream_t s = tpg::as_stream(stream);
-    if (ft == TPG_F64) hipLaunchKernelGGL(k_nonorthogonality<double>, grid, dim3(64 * NR), 0, s, static_cast<const double*>(lambda_ff),
-                                          static_cast<const double*>(phi_ff), immersed, angle, Nx, Ny, Hx, Hy);
-    else               hipLaunchKernelGGL(k_nonorthogonality<float>, grid, dim3(64 * NR), 0, s, static_cast<const float*>(lambda_ff),
-                                          static_cast<const float*>(phi_ff), immersed, angle, Nx, Ny, Hx, Hy);
+    dispatch_ft(ft, [&](auto ty) {
+        typedef decltype(ty) T;
+        hipLaunchKernelGGL(k_nonorthogonality<T>, grid, dim3(64 * NR), 0, s, static_cast<const T*>(lambda_ff), static_cast<const T*>(phi_ff),
+                           immersed, angle, Nx, Ny, Hx, Hy);
+    });
     return tpg::launch_status("k_nonorthogonality");
 }
 
@@ -210,29 +210,24 @@ int tpg_convert_frame(const void* phi_cf, const void* phi_fc, const void* dy_cc,
     tpg::Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     FrameArgs a{ Nx, Ny, Nz, Hx, Hy, Hz, g.sx, g.plane, to_native ? 1 : 0 };
     hipStream_t s = tpg::as_stream(stream);
+    auto launch = [&](auto ty, auto kernel, dim3 grid) {           // the one argument list of both kernels
+        typedef decltype(ty) T;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, static_cast<const T*>(phi_cf), static_cast<const T*>(phi_fc), static_cast<const T*>(dy_cc),
+                           static_cast<const T*>(dx_cc), static_cast<const T*>(u), static_cast<const T*>(v), static_cast<T*>(u_out), static_cast<T*>(v_out), a);
+    };
     const int W = ft == TPG_F64 ? 2 : 4;
     if (Nx % W == 0) {
-        bool aligned = Hx % W == 0;
-        for (const void* q : { u, v, (const void*)u_out, (const void*)v_out }) aligned = aligned && ((uintptr_t)q % 16) == 0;
+        const bool aligned = Hx % W == 0 && rows_on_16B_grid(0, nullptr, 0, u, v, u_out, v_out);
         dim3 grid((unsigned)(((long long)(Nx / W) * Ny + 255) / 256), (Nz + ZCH - 1) / ZCH);      // (chunk, row) jointly; level groups on y
-#define TPG_FRAME_LAUNCH(T, W_, LOOSE_)                                                                                                    \
-        hipLaunchKernelGGL((k_convert_frame_vec<T, W_, LOOSE_>), grid, dim3(256), 0, s, static_cast<const T*>(phi_cf), static_cast<const T*>(phi_fc), \
-                           static_cast<const T*>(dy_cc), static_cast<const T*>(dx_cc), static_cast<const T*>(u), static_cast<const T*>(v),   \
-                           static_cast<T*>(u_out), static_cast<T*>(v_out), a)
-        if (ft == TPG_F64) { if (aligned) TPG_FRAME_LAUNCH(double, 2, false); else TPG_FRAME_LAUNCH(double, 2, true); }
-        else               { if (aligned) TPG_FRAME_LAUNCH(float, 4, false);  else TPG_FRAME_LAUNCH(float, 4, true); }
-#undef TPG_FRAME_LAUNCH
+        dispatch_ft(ft, [&](auto ty) {
+            constexpr int WT = 16 / (int)sizeof(ty);
+            if (aligned) launch(ty, k_convert_frame_vec<decltype(ty), WT, false>, grid);
+            else         launch(ty, k_convert_frame_vec<decltype(ty), WT, true>, grid);
+        });
         return tpg::launch_status("k_convert_frame_vec");
     }
     dim3 grid((Nx + 255) / 256, Ny, (Nz + ZCH - 1) / ZCH);
-    if (ft == TPG_F64)
-        hipLaunchKernelGGL(k_convert_frame<double>, grid, dim3(256), 0, s, static_cast<const double*>(phi_cf), static_cast<const double*>(phi_fc),
-                           static_cast<const double*>(dy_cc), static_cast<const double*>(dx_cc), static_cast<const double*>(u),
-                           static_cast<const double*>(v), static_cast<double*>(u_out), static_cast<double*>(v_out), a);
-    else
-        hipLaunchKernelGGL(k_convert_frame<float>, grid, dim3(256), 0, s, static_cast<const float*>(phi_cf), static_cast<const float*>(phi_fc),
-                           static_cast<const float*>(dy_cc), static_cast<const float*>(dx_cc), static_cast<const float*>(u),
-                           static_cast<const float*>(v), static_cast<float*>(u_out), static_cast<float*>(v_out), a);
+    dispatch_ft(ft, [&](auto ty) { launch(ty, k_convert_frame<decltype(ty)>, grid); });
     return tpg::launch_status("k_convert_frame");
 }
 

@@ -3,7 +3,7 @@
 // TPG_* knob and exports exactly the reference-facing symbols of include/tripolar_hip.h (tests/test_abi.py).  The test
 // library is the same objects plus these hooks: synthetic field fill, the same-shape copy probe of the fold, the knob
 // reload, and the elementary-function probe.
-#include "tpg_zipper_kernels.hpp"
+#include "tpg_launch.hpp"
 #include "../../include/tripolar_hip_test.h"
 
 namespace {
@@ -43,20 +43,15 @@ int tpg_zipper_copy_probe(void* const fields[], int nfields, const int8_t yloc[]
                           int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream,
                           void* start_event, void* stop_event)
 {
-    int rc = tpg::check_geom(Nx, Ny, Nz, Hx, Hy, Hz, ft);
+    int rc = check_call(fields, nfields, Nx, Ny, Nz, Hx, Hy, Hz, ft);
     if (rc) return rc;
-    if ((rc = check_fields(fields, nfields))) return rc;
     if (!yloc) { tpg::set_error("null location table"); return TPG_ERR_INVALID_ARGUMENT; }
     if (nfields > TPG_MAX_FIELDS) { tpg::set_error("copy probe: at most %d fields (one kernel)", TPG_MAX_FIELDS); return TPG_ERR_UNSUPPORTED; }
     int8_t xl[TPG_MAX_FIELDS]; int32_t sg[TPG_MAX_FIELDS];
     for (int f = 0; f < nfields; ++f) { xl[f] = TPG_CENTER; sg[f] = 1; }
     Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
-    tpg::ev_start = static_cast<hipEvent_t>(start_event);
-    tpg::ev_stop = static_cast<hipEvent_t>(stop_event);
-    rc = (ft == TPG_F64) ? zipper_batch<double, true>(fields, nfields, xl, yloc, sg, g, 1, Nz, tpg::as_stream(stream))
-                         : zipper_batch<float, true>(fields, nfields, xl, yloc, sg, g, 1, Nz, tpg::as_stream(stream));
-    tpg::ev_start = tpg::ev_stop = nullptr;
-    return rc;
+    TimedScope timed(start_event, stop_event);
+    return dispatch_ft(ft, [&](auto ty) { return zipper_batch<decltype(ty), true>(fields, nfields, xl, yloc, sg, g, 1, Nz, tpg::as_stream(stream)); });
 }
 
 int tpg_fill_synthetic(void* field, uint64_t seed, double halo_sentinel,
@@ -67,8 +62,9 @@ int tpg_fill_synthetic(void* field, uint64_t seed, double halo_sentinel,
     if (!field) { tpg::set_error("null field"); return TPG_ERR_INVALID_ARGUMENT; }
     Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     hipStream_t s = tpg::as_stream(stream);
-    if (ft == TPG_F64) hipLaunchKernelGGL(k_synthetic<double>, dim3(256 * 16), dim3(256), 0, s, static_cast<double*>(field), seed, halo_sentinel, g);
-    else               hipLaunchKernelGGL(k_synthetic<float>, dim3(256 * 16), dim3(256), 0, s, static_cast<float*>(field), seed, halo_sentinel, g);
+    dispatch_ft(ft, [&](auto ty) {
+        hipLaunchKernelGGL(k_synthetic<decltype(ty)>, dim3(256 * 16), dim3(256), 0, s, static_cast<decltype(ty)*>(field), seed, halo_sentinel, g);
+    });
     return tpg::launch_status("k_synthetic");
 }
 

@@ -16,7 +16,7 @@
 // plain form (every row on the 16-B grid) moves aligned 16-B vectors and the GEN form (element-aligned 16-B chunks, the last chunk of a
 // row moved back to end at the row's end: Float32 rows of 3610 at halo 5, offset pointers, rows shorter than a chunk) serves the rest; an
 // overlapping chunk computes the same values from the same sources.
-#include "tpg_zipper_kernels.hpp"
+#include "tpg_launch.hpp"
 
 namespace {
 
@@ -74,14 +74,6 @@ __global__ __launch_bounds__(256) void k_value_gradient(VGTable t, VGArgs a)
     *reinterpret_cast<cvec_t*>(c + a.plane * pd + (long long)a.sx * jd + e0) = out;
 }
 
-template <typename T>
-void vg_launch(dim3 grid, hipStream_t s, const VGTable& t, const VGArgs& a, int W, bool gen)
-{
-    if (!gen)        hipLaunchKernelGGL((k_value_gradient<T, 16 / sizeof(T), false>), grid, dim3(256), 0, s, t, a);
-    else if (W == 2) hipLaunchKernelGGL((k_value_gradient<T, 2, true>), grid, dim3(256), 0, s, t, a);
-    else             hipLaunchKernelGGL((k_value_gradient<T, 16 / sizeof(T), true>), grid, dim3(256), 0, s, t, a);
-}
-
 }  // namespace
 
 extern "C" {
@@ -90,9 +82,8 @@ int tpg_fill_value_gradient_halos(void* const fields[], int nfields, int pass, c
                                   const void* const conditions[], const void* dy_cf, double dz_bottom, double dz_top,
                                   int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
-    int rc = tpg::check_geom(Nx, Ny, Nz, Hx, Hy, Hz, ft);
+    int rc = check_call(fields, nfields, Nx, Ny, Nz, Hx, Hy, Hz, ft);
     if (rc) return rc;
-    if ((rc = check_fields(fields, nfields))) return rc;
     if (!kinds || !values || !conditions) { tpg::set_error("null kinds, values or conditions table"); return TPG_ERR_INVALID_ARGUMENT; }
     const int zbits = TPG_SIDE_BOTTOM | TPG_SIDE_TOP;
     if (pass != TPG_SIDE_SOUTH && ((pass & ~zbits) || !(pass & zbits))) {
@@ -136,11 +127,11 @@ int tpg_fill_value_gradient_halos(void* const fields[], int nfields, int pass, c
     Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     // plain 16-B chunks where every row starts on the 16-B grid, element-aligned 16-B (or, for rows shorter than 16 B, 8-B) chunks otherwise
     const int WMAX = (int)(16 / esz);
-    bool plain = ((size_t)g.sx * esz) % 16 == 0 && (!south || (uintptr_t)dy_cf % 16 == 0);
+    bool plain = rows_on_16B_grid((size_t)g.sx * esz, nullptr, 0, south ? dy_cf : nullptr);
     for (int f = 0; f < nfields && plain; ++f)
         for (int q = 0; q < 2; ++q)
             if (side[q] >= 0 && kinds[3 * f + side[q]])
-                plain = plain && (uintptr_t)fields[f] % 16 == 0 && (uintptr_t)conditions[3 * f + side[q]] % 16 == 0;
+                plain = plain && rows_on_16B_grid(0, nullptr, 0, fields[f], conditions[3 * f + side[q]]);
     const int W = plain || g.sx >= WMAX ? WMAX : 2;
     const int cpr = plain ? g.sx / W : (g.sx + W - 1) / W;
     const long long max_rows = south ? (long long)Nz : 2ll * g.sy;
@@ -173,8 +164,11 @@ int tpg_fill_value_gradient_halos(void* const fields[], int nfields, int pass, c
         }
         if (n == 0) break;
         dim3 grid((unsigned)((rows * cpr + 255) / 256), (unsigned)n);
-        if (ft == TPG_F64) vg_launch<double>(grid, s, t, a, W, !plain);
-        else               vg_launch<float>(grid, s, t, a, W, !plain);
+        dispatch_ft(ft, [&](auto ty) {
+            dispatch_chunk<decltype(ty)>(W, !plain, [&](auto w, auto gen) {
+                hipLaunchKernelGGL((k_value_gradient<decltype(ty), decltype(w)::value, decltype(gen)::value>), grid, dim3(256), 0, s, t, a);
+            });
+        });
         if ((rc = tpg::launch_status("k_value_gradient"))) return rc;
     }
     return TPG_OK;

@@ -1,7 +1,8 @@
-// tpg_zipper_kernels.hpp -- device kernels and launch helpers of the halo fill (zipper fold, periodic x, fused / merged
-// fills, seam pack / unpack).  Included by tpg_zipper.hip (the product entry points) and by tpg_testabi.hip (the
-// test / bench-only entry points of libtripolar_hip_test.so, which instantiate the COPY = true probe form of the column
-// kernel); everything here has internal linkage.
+// tpg_zipper_kernels.hpp -- device kernels of the halo fill (zipper fold, periodic x, fused / merged fills, seam pack /
+// unpack) and their argument structs; the host code that chooses and launches them is tpg_launch.hpp, which includes this
+// file.  Reaches tpg_zipper.hip (the product entry points) and tpg_testabi.hip (the test / bench-only entry points of
+// libtripolar_hip_test.so, which instantiate the COPY = true probe form of the column kernel) that way; everything here
+// has internal linkage.
 #pragma once
 #include "tpg_common.hpp"
 #include <hip/hip_ext.h>
@@ -610,151 +611,6 @@ __global__ __launch_bounds__(256) void k_pack_loose(PtrTable pt, T* buffer, Pack
         *reinterpret_cast<lvec_t*>(dst) = *reinterpret_cast<const lvec_t*>(src);
     } else {
         for (int v = 0; v < slab - e0; ++v) dst[v] = src[v];
-    }
-}
-
-int check_fields(void* const fields[], int nfields)
-{
-    if (!fields || nfields < 1) { tpg::set_error("no fields"); return TPG_ERR_INVALID_ARGUMENT; }
-    for (int f = 0; f < nfields; ++f)
-        if (!fields[f]) { tpg::set_error("null field %d", f); return TPG_ERR_INVALID_ARGUMENT; }
-    return TPG_OK;
-}
-
-#define TPG_LAUNCH(kernel, grid, block, stream, ...)                                                            \
-    do {                                                                                                        \
-        if (tpg::ev_start || tpg::ev_stop) {                                                                    \
-            hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, tpg::ev_start, tpg::ev_stop, 0, __VA_ARGS__); \
-            tpg::ev_start = tpg::ev_stop = nullptr;                                                             \
-        } else                                                                                                  \
-            hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                                    \
-    } while (0)
-
-// Which instantiation of the chunked kernels serves this geometry and these pointers.  Plain (gen = false): Hx and Nx whole numbers of
-// 16-B chunks and every field 16-B aligned -- the geometry of the defaults, halo (4, 4, 4).  GEN (see the note above) for everything else:
-// an odd Hx (the reference's model halo (5, 5, 5)), 16-B-misaligned pointers, and -- with 8-B chunks, W = 2 -- Float32 rows with
-// Nx = 2 mod 4.  Nx is even (tripolar_grid.jl:81-83), so W = 2 always divides it: every geometry has a chunked form.
-struct ChunkPlan { int W; bool gen; };
-template <typename T>
-ChunkPlan chunk_plan(const Geom& g, void* const fields[], int n)
-{
-    constexpr int WMAX = 16 / (int)sizeof(T);
-    bool plain = g.Hx % WMAX == 0 && g.Nx % WMAX == 0;
-    for (int f = 0; f < n && plain; ++f) plain = ((uintptr_t)fields[f] % 16) == 0;
-    if (plain) return { WMAX, false };
-    return { g.Nx % WMAX == 0 ? WMAX : 2, true };
-}
-
-template <typename T, int W, bool COPY, bool GEN>
-void launch_cols(int Hy, dim3 grid, hipStream_t s, const FieldTable& ft, const ZipArgs& a)
-{
-    switch (Hy) {
-    case 1: TPG_LAUNCH((k_zipper_cols<T, W, 1, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    case 2: TPG_LAUNCH((k_zipper_cols<T, W, 2, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    case 3: TPG_LAUNCH((k_zipper_cols<T, W, 3, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    case 4: TPG_LAUNCH((k_zipper_cols<T, W, 4, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    case 5: TPG_LAUNCH((k_zipper_cols<T, W, 5, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    case 6: TPG_LAUNCH((k_zipper_cols<T, W, 6, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    case 7: TPG_LAUNCH((k_zipper_cols<T, W, 7, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    default: TPG_LAUNCH((k_zipper_cols<T, W, 8, COPY, GEN>), grid, dim3(256), s, ft, a); break;
-    }
-}
-
-// Kernel choice: column items (k_zipper_cols, plain or GEN: chunk_plan) for Hy <= 8; row items otherwise
-// (k_zipper_vec for Hy > 8 -- e.g. the extended north halo of the split-explicit free surface -- on the plain geometry, k_zipper_scalar
-// for Hy > 8 elsewhere and for Hy = 0).  TPG_ZIPPER_VARIANT=0 forces the row kernels everywhere (cross-check,
-// tests/test_gpu_variants.py).  What was measured and dropped (tools/fillbench, profiles/r02/fillbench_ab.txt):
-// plain loads (cold-dirty 26 vs 20 us), non-temporal stores (+2 us), write-through sc1 / sc0 sc1 buffer stores
-// (-0.5 us cold-clean, +0 dirty), a persistent software-pipelined grid (1024 blocks, loads of item n+1 ahead of the
-// stores of item n: -0.5 us), two half-row chunks per thread (one resident round of 4224 waves: +-0), 512 / 1024-thread
-// blocks, two levels per thread (slower).  All of them, and same-shape pure copies, sit at 14.7-16.1 us cold:
-// the 73 MB launch is at the copy ceiling of this access shape.
-template <typename T, bool COPY = false>
-int zipper_batch(void* const fields[], int n, const int8_t xloc[], const int8_t yloc[], const int32_t sign[],
-                 const Geom& g, int kstart, int kcount, hipStream_t s)
-{
-    constexpr int WMAX = 16 / (int)sizeof(T);
-    const ChunkPlan cp = chunk_plan<T>(g, fields, n);
-    const int W = cp.W;
-    const bool vec = !cp.gen;                                        // the row-item kernel k_zipper_vec exists in the plain form only
-    const bool cols = g.Hy >= 1 && g.Hy <= 8 && (COPY ? vec : tpg::config().zipper_variant != 0);    // Hy = 0: only the row-Ny substitution remains (row kernels)
-    if (COPY && !cols) { tpg::set_error("copy probe: geometry has no plain column kernel"); return TPG_ERR_UNSUPPORTED; }
-
-    FieldTable ft;
-    ZipArgs a;
-    a.Nx = g.Nx; a.Ny = g.Ny; a.Hx = g.Hx; a.Hy = g.Hy; a.Hz = g.Hz; a.sx = g.sx; a.plane = g.plane;
-    a.kstart = kstart; a.kcount = kcount;
-    const bool chunked = cols || vec;
-    a.nchunks = chunked ? g.Nx / W : g.Nx;
-    a.fix0 = chunked ? (g.Nx / 2) / W : g.Nx / 2;      // first chunk / element (0-based) holding an i > Nx/2
-    ft.nfields = n;
-    long long total = 0;
-    for (int f = 0; f < n; ++f) {
-        ft.ptr[f] = fields[f]; ft.xloc[f] = xloc[f]; ft.yloc[f] = yloc[f]; ft.sign[f] = sign[f];
-        ft.item0[f] = (int)total;
-        long long per_level = cols ? a.nchunks
-                                   : (long long)g.Hy * a.nchunks + (yloc[f] == TPG_CENTER ? a.nchunks - a.fix0 : 0);
-        total += per_level * kcount;
-        if (total >= (1ll << 31)) { tpg::set_error("zipper batch too large for 32-bit item index"); return TPG_ERR_UNSUPPORTED; }
-    }
-    ft.item0[n] = (int)total;
-    if (total == 0) return TPG_OK;
-    dim3 grid((unsigned)((total + 255) / 256));
-    if (cols) {
-        dim3 grid2((unsigned)(((long long)kcount * a.nchunks + 255) / 256), (unsigned)n);
-        if constexpr (COPY) {
-            launch_cols<T, WMAX, true, false>(g.Hy, grid2, s, ft, a);
-        } else if constexpr (sizeof(T) == 8) {
-            if (cp.gen) launch_cols<T, 2, false, true>(g.Hy, grid2, s, ft, a);
-            else        launch_cols<T, 2, false, false>(g.Hy, grid2, s, ft, a);
-        } else {
-            if (W == 2)      launch_cols<T, 2, false, true>(g.Hy, grid2, s, ft, a);
-            else if (cp.gen) launch_cols<T, 4, false, true>(g.Hy, grid2, s, ft, a);
-            else             launch_cols<T, 4, false, false>(g.Hy, grid2, s, ft, a);
-        }
-    }
-    else if (vec) TPG_LAUNCH((k_zipper_vec<T, WMAX>), grid, dim3(256), s, ft, a);
-    else          TPG_LAUNCH((k_zipper_scalar<T>), grid, dim3(256), s, ft, a);
-    return tpg::launch_status("k_zipper");
-}
-
-template <typename T, int W, bool GEN>
-int merged_batch(const FieldTable& t, const MergedArgs& a, int n, int Hy, hipStream_t s)
-{
-    const long long itemsB = a.rowsB * a.hw;
-    dim3 grid(a.blocksA + a.blocksS + (unsigned)((itemsB + 255) / 256), (unsigned)n);
-    switch (Hy) {
-    case 1: TPG_LAUNCH((k_fill_merged<T, W, 1, GEN>), grid, dim3(256), s, t, a); break;
-    case 2: TPG_LAUNCH((k_fill_merged<T, W, 2, GEN>), grid, dim3(256), s, t, a); break;
-    case 3: TPG_LAUNCH((k_fill_merged<T, W, 3, GEN>), grid, dim3(256), s, t, a); break;
-    case 4: TPG_LAUNCH((k_fill_merged<T, W, 4, GEN>), grid, dim3(256), s, t, a); break;
-    case 5: TPG_LAUNCH((k_fill_merged<T, W, 5, GEN>), grid, dim3(256), s, t, a); break;
-    case 6: TPG_LAUNCH((k_fill_merged<T, W, 6, GEN>), grid, dim3(256), s, t, a); break;
-    case 7: TPG_LAUNCH((k_fill_merged<T, W, 7, GEN>), grid, dim3(256), s, t, a); break;
-    default: TPG_LAUNCH((k_fill_merged<T, W, 8, GEN>), grid, dim3(256), s, t, a); break;
-    }
-    return tpg::launch_status("k_fill_merged");
-}
-
-// the (T, W, GEN) instantiations that exist: Float64 16-B chunks plain / GEN; Float32 16-B chunks plain / GEN, 8-B chunks GEN only
-template <typename T>
-int merged_dispatch(const FieldTable& t, const MergedArgs& a, int n, int Hy, ChunkPlan cp, hipStream_t s)
-{
-    if constexpr (sizeof(T) == 8) return cp.gen ? merged_batch<T, 2, true>(t, a, n, Hy, s) : merged_batch<T, 2, false>(t, a, n, Hy, s);
-    else if (cp.W == 2) return merged_batch<T, 2, true>(t, a, n, Hy, s);
-    else return cp.gen ? merged_batch<T, 4, true>(t, a, n, Hy, s) : merged_batch<T, 4, false>(t, a, n, Hy, s);
-}
-
-template <typename T>
-void fused_vec_dispatch(dim3 grid, hipStream_t s, const FieldTable& t, const FusedVecArgs& v, ChunkPlan cp)
-{
-    if constexpr (sizeof(T) == 8) {
-        if (cp.gen) TPG_LAUNCH((k_fill_fused_vec<T, 2, true>), grid, dim3(256), s, t, v);
-        else        TPG_LAUNCH((k_fill_fused_vec<T, 2, false>), grid, dim3(256), s, t, v);
-    } else {
-        if (cp.W == 2)   TPG_LAUNCH((k_fill_fused_vec<T, 2, true>), grid, dim3(256), s, t, v);
-        else if (cp.gen) TPG_LAUNCH((k_fill_fused_vec<T, 4, true>), grid, dim3(256), s, t, v);
-        else             TPG_LAUNCH((k_fill_fused_vec<T, 4, false>), grid, dim3(256), s, t, v);
     }
 }
 

@@ -227,3 +227,101 @@ def test_cell_kernel_stores_are_all_streaming(tmp_path):
         assert len(stores) >= nmin and not plain, (kernel, T, len(stores), plain[:5])
         found += 1
     assert found == 2
+
+
+# ---- invalid calls: every one returns before any device work, with one (status, message) pair ---------------------------------------
+_FILL_GEOMETRIES = {                                               # Nx, Ny, Nz, Hx, Hy, Hz: one per launch strategy of tpg_fill_halo_regions
+    "fused": (10, 10, 1, 4, 4, 4),                                 # small: the one fused launch
+    "merged": (3600, 1800, 75, 4, 4, 4),                           # items x nfields > 2^20, Hy <= 8: the merged launch
+    "two_launch_hy0": (10, 10, 1, 4, 0, 4),                        # no north halo rows
+    "two_launch_hy9": (40, 40, 1, 4, 9, 4),                        # more rows than the column kernels have
+    "two_launch_narrow": (8, 10, 1, 4, 4, 4),                      # Nx < 2 Hx + 2
+}
+_COMMON_FAULTS = ("odd_nx", "bad_ft", "no_fields", "null_field")
+_TABLE_FAULTS = _COMMON_FAULTS + ("null_tables", "location_3")
+
+
+def _invalid_calls():
+    """(label, entry point, arguments) of calls that must fail in argument validation"""
+    P = 1 << 20                                                    # a non-NULL pointer that is never dereferenced
+    good = (C.c_void_p * 1)(P)
+    null_field = (C.c_void_p * 1)(None)
+    xl, yl, sg = (C.c_int8 * 1)(0), (C.c_int8 * 1)(0), (C.c_int32 * 1)(1)
+    xl3 = (C.c_int8 * 1)(3)
+
+    def head(fault):                                               # fields, nfields
+        return {"no_fields": (good, 0), "null_field": (null_field, 1)}.get(fault, (good, 1))
+
+    def tables(fault):
+        return {"null_tables": (None, None, None), "location_3": (xl3, yl, sg)}.get(fault, (xl, yl, sg))
+
+    def geom(g, fault):
+        return (g[0] + 1,) + g[1:] if fault == "odd_nx" else g
+
+    def ft(fault):
+        return 7 if fault == "bad_ft" else 1
+
+    calls = []
+    for gname, g in _FILL_GEOMETRIES.items():
+        for fault in _TABLE_FAULTS:
+            calls.append((f"fill_halo_regions/{gname}/{fault}", "tpg_fill_halo_regions",
+                          (*head(fault), *tables(fault), *geom(g, fault), 1, ft(fault), None)))
+        # without a zipper the tables may be NULL: only the geometry and the fields are looked at
+        calls.append((f"fill_halo_regions/{gname}/no_zipper_null_tables_null_field", "tpg_fill_halo_regions",
+                      (null_field, 1, None, None, None, *g, 0, 1, None)))
+    g = _FILL_GEOMETRIES["fused"]
+    for fault in _TABLE_FAULTS:
+        calls.append((f"zipper_fill/{fault}", "tpg_zipper_fill", (*head(fault), *tables(fault), *geom(g, fault), 1, 1, ft(fault), None)))
+    for fault in _COMMON_FAULTS:
+        calls.append((f"periodic_x_fill/{fault}", "tpg_periodic_x_fill", (*head(fault), *geom(g, fault), ft(fault), None)))
+        calls.append((f"pack_y_halo/{fault}", "tpg_pack_y_halo", (*head(fault), P, 0, *geom(g, fault), ft(fault), None)))
+        calls.append((f"fill_bounded_halos/{fault}", "tpg_fill_bounded_halos", (*head(fault), (C.c_uint8 * 1)(7), *geom(g, fault), ft(fault), None)))
+        calls.append((f"fill_value_gradient_halos/{fault}", "tpg_fill_value_gradient_halos",
+                      (*head(fault), 1, (C.c_uint8 * 3)(1, 0, 0), (C.c_double * 3)(), (C.c_void_p * 3)(), P, 1.0, 1.0, *geom(g, fault), ft(fault), None)))
+    calls.append(("pack_y_halo/null_buffer", "tpg_pack_y_halo", (good, 1, None, 0, *g, 1, None)))
+    calls.append(("pack_y_halo/side_2", "tpg_pack_y_halo", (good, 1, P, 2, *g, 1, None)))
+    calls.append(("fill_bounded_halos/null_sides", "tpg_fill_bounded_halos", (good, 1, None, *g, 1, None)))
+    calls.append(("fill_value_gradient_halos/null_tables", "tpg_fill_value_gradient_halos",
+                  (good, 1, 1, None, None, None, P, 1.0, 1.0, *g, 1, None)))
+    # the four (rank, nranks) forms with rank = nranks
+    msg = (None, None, None, None)
+    calls.append(("halo_exchange_y/rank_is_nranks", "tpg_halo_exchange_y", (None, 2, 2, good, 1, *msg, *g, 1, None)))
+    calls.append(("halo_exchange_y_pipelined/rank_is_nranks", "tpg_halo_exchange_y_pipelined", (None, 2, 2, good, 1, *msg, *g, 1, None, None, 1)))
+    calls.append(("fill_halo_regions_distributed/rank_is_nranks", "tpg_fill_halo_regions_distributed",
+                  (None, 2, 2, good, 1, xl, yl, sg, *msg, *g, 1, None)))
+    calls.append(("fill_halo_regions_distributed_pipelined/rank_is_nranks", "tpg_fill_halo_regions_distributed_pipelined",
+                  (None, 2, 2, good, 1, xl, yl, sg, *msg, *g, 1, None, None, 1)))
+    return calls
+
+
+def _invalid_call_results(lib):
+    return {label: (getattr(lib, fn)(*args), lib.tpg_last_error().decode()) for label, fn, args in _invalid_calls()}
+
+
+# recorded from a build of the commit before the host launch layer was shared (csrc/tpg_launch.hpp), through _invalid_call_results();
+# every entry point and every launch strategy of tpg_fill_halo_regions gave one and the same pair per fault
+_EXPECTED_BY_FAULT = {
+    "odd_nx": (-2, "The number of cells in the longitude dimension should be even!"),
+    "bad_ft": (-1, "unknown element type ft=7"),
+    "no_fields": (-1, "no fields"),
+    "null_field": (-1, "null field 0"),
+    "null_tables": (-1, "null location/sign table"),
+    "location_3": (-1, "field 0: no zipper method for location (3,0)"),
+    "no_zipper_null_tables_null_field": (-1, "null field 0"),
+    "null_buffer": (-1, "null message buffer"),
+    "side_2": (-1, "side must be 0 (south) or 1 (north)"),
+    "null_sides": (-1, "null sides table"),
+    "rank_is_nranks": (-3, "rank 2 outside 0:1"),
+}
+_EXPECTED_BY_LABEL = {"fill_value_gradient_halos/null_tables": (-1, "null kinds, values or conditions table")}
+
+
+def test_invalid_calls_keep_their_status_and_message(osg):
+    """Characterisation of the argument validation: tpg_fill_halo_regions validates once, before it chooses between its fused, merged
+    and two-launch strategies, and must answer every fault exactly as each strategy's own checks used to -- same status, same
+    tpg_last_error() text -- for a geometry of each strategy; likewise the other fill entry points and the (rank, nranks) forms."""
+    got = _invalid_call_results(osg._lib.lib())
+    assert len(got) == 5 * 7 + 6 + 4 * 4 + 4 + 4
+    for label, pair in got.items():
+        want = _EXPECTED_BY_LABEL.get(label, _EXPECTED_BY_FAULT[label.rsplit("/", 1)[1]])
+        assert pair == want, (label, pair, want)

@@ -4,8 +4,10 @@
 
 OLD_DIR / NEW_DIR hold the objects of csrc/ (e.g. a copy of csrc/*.o taken at the parent commit, and csrc/ itself).  For every
 object (default: every *.o in OLD_DIR) the device code object is taken out of the .hip_fatbin section (llvm-objcopy +
-clang-offload-bundler), disassembled (llvm-objdump -d) and compared per kernel symbol.  Prints one JSON line: per object, whether
-the code objects are byte-identical and the kernels whose disassembly differs or that exist on one side only."""
+clang-offload-bundler), disassembled (llvm-objdump -d) and compared per kernel symbol, together with the kernel's descriptor metadata
+(llvm-readelf --notes: register counts, spills, LDS, scratch and kernarg size).  Prints one JSON line: per object, whether the code
+objects are byte-identical and the kernels whose disassembly or metadata differs or that exist on one side only; exit status 0 only
+if there is none of either."""
 import json
 import os
 import re
@@ -47,6 +49,26 @@ def kernels(co):
     return syms
 
 
+DESCRIPTOR = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size",
+              "private_segment_fixed_size", "kernarg_segment_size", "max_flat_workgroup_size", "uses_dynamic_stack")
+
+
+def descriptors(co):
+    """symbol -> the DESCRIPTOR entries of its amdhsa.kernels record"""
+    out = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+    recs, cur = [], None
+    for line in out.splitlines():
+        m = re.match(r"^(  - |    )\.(\w+):\s+(\S.*)$", line)           # scalar entries of a kernel record (its .args are nested deeper)
+        if not m:
+            continue
+        if m.group(1) == "  - ":
+            cur = {}
+            recs.append(cur)
+        if cur is not None:
+            cur[m.group(2)] = m.group(3).strip()
+    return {r["name"]: {k: r.get(k) for k in DESCRIPTOR} for r in recs if "name" in r}
+
+
 def main():
     old_dir, new_dir = sys.argv[1], sys.argv[2]
     names = sys.argv[3:] or sorted(n for n in os.listdir(old_dir) if n.endswith(".o"))
@@ -61,11 +83,15 @@ def main():
             co_a, a = code_object(os.path.join(old_dir, n), os.path.join(tmp, "old"))
             co_b, b = code_object(os.path.join(new_dir, n), os.path.join(tmp, "new"))
             ka, kb = kernels(co_a), kernels(co_b)
-            report[n] = {"code_object_identical": a == b, "kernels": len(ka),
+            da, db = descriptors(co_a), descriptors(co_b)
+            assert da and set(da) <= set(ka), "kernel metadata of " + n + " not understood"
+            report[n] = {"code_object_identical": a == b, "kernels": len(ka), "descriptors": len(da),
                          "differing": sorted(k for k in ka if k in kb and ka[k] != kb[k]),
+                         "metadata_differing": sorted(k for k in set(da) | set(db) if da.get(k) != db.get(k)),
                          "only_old": sorted(set(ka) - set(kb)), "only_new": sorted(set(kb) - set(ka))}
     print(json.dumps(report))
-    return 0 if all(not r.get("differing") and not r.get("only_old") for r in report.values()) else 1
+    bad = ("differing", "metadata_differing", "only_old", "only_new")
+    return 0 if all(not any(r.get(k) for k in bad) for r in report.values()) else 1
 
 
 if __name__ == "__main__":

@@ -35,7 +35,8 @@ def main():
     from bench_common import sources_sha16
     csrc = "orthogonalsphericalshellgrids.jl_amd/csrc/"
     grid_src = [csrc + f for f in ("tpg_grid.hip", "tpg_batch.hpp", "tpg_math.hpp")]
-    fill_src = [csrc + f for f in ("tpg_zipper_kernels.hpp", "tpg_zipper.hip")]
+    # the launch layer is part of the key: launch geometry decides traffic as much as kernel text does
+    fill_src = [csrc + f for f in ("tpg_zipper_kernels.hpp", "tpg_launch.hpp", "tpg_zipper.hip")]
     sources = {"k_tables": grid_src, "k_cells_tile": grid_src, "k_cells": grid_src, "k_halos": grid_src, "k_south": grid_src,
                "k_fill_merged": fill_src, "k_zipper_cols": fill_src, "k_periodic_x_vec": fill_src, "k_fill_fused_vec": fill_src,
                "k_zipper_cols_copy_probe": fill_src, "k_pack": fill_src, "k_synthetic": [csrc + "tpg_testabi.hip"]}
