@@ -223,6 +223,36 @@ int tpg_fill_value_gradient_halos(void *const fields[], int nfields, int pass, c
                                   const void *const conditions[], const void *dy_cf, double dz_bottom, double dz_top,
                                   int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
 
+/* ---- Open (impenetrable) south, bottom and top faces -----------------------------------------
+ * Oceananigans' fill of an Open-class condition (OpenBoundaryCondition(v); ImpenetrableBoundaryCondition() = BoundaryCondition(Open(),
+ * nothing), which its models put on the wall-normal velocities: v (Center, Face, Center) south, w (Center, Center, Face) bottom and
+ * top) [recalled: fill_open_boundary_regions!; parity unpinned]: the boundary-normal velocity is written ON THE BOUNDARY FACE ITSELF --
+ * for a Face-located field an INTERIOR cell -- and no halo cell of that side is touched.  1-based, Nz the field's own level count (grid
+ * Nz + 1 for a field at Face in z):
+ *     TPG_SIDE_SOUTH   c[i, 1, k]  = v     i = 1-Hx..Nx+Hx, k = 1..Nz      for a field at (Center, Face, Center)
+ *     TPG_SIDE_BOTTOM  c[i, j, 1]  = v     i = 1-Hx..Nx+Hx, j = 1..Ny      for a field at (Center, Center, Face)
+ *     TPG_SIDE_TOP     c[i, j, Nz] = v     i = 1-Hx..Nx+Hx, j = 1..Ny      for a field at (Center, Center, Face)
+ * v is 0 for an impenetrable side, otherwise the prescribed normal velocity (an FT value).  Rows j <= 0 and j >= Ny+1, planes k <= 0 and
+ * k >= Nz+1 are not written.  A PRE-PASS: call it BEFORE the horizontal fill of the same fields (tpg_fill_halo_regions, tpg_zipper_fill
+ * + tpg_periodic_x_fill, a tpg_fill_halo_regions_distributed* call, or the pack of a host-driven seam exchange), which folds the written
+ * rows into the north halo, carries them into the x halos (overwriting the x-halo columns written here) and to the neighbour band; the
+ * whole order is  Open faces -> horizontal fill (-> seam exchange) -> Value / Gradient south -> tpg_fill_bounded_halos -> Value /
+ * Gradient bottom / top.  The location is the caller's to check: this call writes the sides it is given.  Where one field has
+ * TPG_SIDE_SOUTH and a z side, the cells both own (c[i, 1, 1], c[i, 1, Nz]) take the z side's value.
+ * Unpinned: another reading of Oceananigans makes the same face write inside its regular south / bottom-top kernels; the two agree on
+ * every cell for a scalar v when the field's other sides are a model's defaults, and can differ only in rows j <= 0 of the face planes
+ * of a w field without a south condition and in what the halo entries of an array condition mean.  This is the first reading.
+ * sides[f] is an OR of the TPG_SIDE_* bits of field f.  Per field f and side s (0 south, 1 bottom, 2 top) the condition is
+ * conditions[3f+s], a device array of FT read at call time, or, where that is NULL, values[3f+s] (a double holding an FT value):
+ *     south: (Nz, Nx+2Hx) array, entry [k-1][i+Hx-1];  bottom / top: (Ny+2Hy, Nx+2Hx), entry [j+Hy-1][i+Hx-1], rows j = 1..Ny read.
+ * ONE launch per batch of up to TPG_MAX_FIELDS fields that have a side (more are split); Float32 and Float64, every halo width, every
+ * pointer aligned to the element type; capturable into a HIP graph.  No field with a side: TPG_OK, no launch.  Every check precedes
+ * any launch: TPG_ERR_INVALID_ARGUMENT for a sides value with other bits, a null table or a field / condition pointer off its element
+ * alignment; TPG_ERR_UNSUPPORTED for TPG_SIDE_SOUTH with Ny < 2 (row 1 is then the zipper's row Ny), for TPG_SIDE_BOTTOM and
+ * TPG_SIDE_TOP on one field with Nz < 2 (one plane) and for a launch too large for 32-bit work-item indices. */
+int tpg_fill_open_faces(void *const fields[], int nfields, const uint8_t sides[], const double values[],
+                        const void *const conditions[], int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
+
 /* ---- latitude-band halo exchange helpers (config 4) -------------------------------------
  * The interior seams of a y-slab partition exchange Hy full rows (all i incl. x halos, all
  * levels incl. z halos) per side and field; the transport (RCCL send/recv, ROCm-aware MPI) stays

@@ -10,6 +10,7 @@ from .boundary_conditions import (BoundaryCondition, Center, Face, FieldBoundary
                                   ZipperBoundaryCondition, PeriodicBoundaryCondition, bc_str,
                                   Flux, FluxBoundaryCondition, NoFluxBoundaryCondition,
                                   Value, ValueBoundaryCondition, Gradient, GradientBoundaryCondition,
+                                  Open, OpenBoundaryCondition, ImpenetrableBoundaryCondition, is_open,
                                   apply_y_north_bc, regularize_field_boundary_conditions, sign,
                                   validate_boundary_condition_location, is_flux, is_gradient, is_value,
                                   is_zipper)

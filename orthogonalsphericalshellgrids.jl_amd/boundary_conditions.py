@@ -78,6 +78,21 @@ class Gradient(AbstractBoundaryConditionClassification):
         return hash(Gradient)
 
 
+class Open(AbstractBoundaryConditionClassification):
+    """Oceananigans' Open classification [recalled]: a prescribed boundary-normal velocity, written on the boundary face itself (an interior
+    cell of a Face-located field); no halo cell of the side is touched.  A model's wall-normal velocities carry it with condition None
+    (impenetrable): v on its south side, w on its bottom and top sides: tpg_fill_open_faces."""
+
+    def __repr__(self):
+        return "Open()"
+
+    def __eq__(self, other):
+        return isinstance(other, Open)
+
+    def __hash__(self):
+        return hash(Open)
+
+
 @dataclass(frozen=True)
 class BoundaryCondition:
     classification: Any
@@ -117,6 +132,16 @@ def GradientBoundaryCondition(condition):
     return BoundaryCondition(Gradient(), condition)
 
 
+def OpenBoundaryCondition(condition=None):
+    """OpenBoundaryCondition(v) = BoundaryCondition(Open(), v): the boundary-normal velocity v   [recalled, Oceananigans]"""
+    return BoundaryCondition(Open(), condition)
+
+
+def ImpenetrableBoundaryCondition():
+    """ImpenetrableBoundaryCondition() = BoundaryCondition(Open(), nothing): zero normal velocity   [recalled, Oceananigans]"""
+    return OpenBoundaryCondition(None)
+
+
 def is_flux(bc):
     return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Flux)
 
@@ -128,6 +153,11 @@ def is_value(bc):
 
 def is_gradient(bc):
     return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Gradient)
+
+
+def is_open(bc):
+    """the library's own Open classification (isinstance: another class that happens to be named Open is not it)"""
+    return isinstance(bc, BoundaryCondition) and isinstance(bc.classification, Open)
 
 
 def is_zipper(bc):

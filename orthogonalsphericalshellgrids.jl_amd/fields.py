@@ -7,7 +7,8 @@ Field data is one torch tensor of shape (Nz'+2Hz, Ny+2Hy, Nx+2Hx) in HBM whose m
 one geometry into ONE zipper launch + one periodic-x launch, or into a single fused launch when the
 fields are small (tpg_fill_halo_regions); fields with no-flux south / bottom / top sides get one more launch after the horizontal
 fill (tpg_fill_bounded_halos); fields with Value / Gradient south / bottom / top sides get one launch before that mirror (south) and one after
-it (bottom / top): tpg_fill_value_gradient_halos.
+it (bottom / top): tpg_fill_value_gradient_halos; fields with Open (impenetrable) south / bottom / top sides -- a model's v and w -- get one
+launch BEFORE the horizontal fill, which writes the boundary face itself: tpg_fill_open_faces.
 """
 import ctypes as C
 import numbers
@@ -17,7 +18,7 @@ import torch
 from . import _lib
 from .boundary_conditions import (Center, Face, FieldBoundaryConditions, PeriodicBoundaryCondition,
                                   ZipperBoundaryCondition, HaloCommunicationBoundaryCondition,
-                                  is_flux, is_gradient, is_value, is_zipper, sign)
+                                  is_flux, is_gradient, is_open, is_value, is_zipper, sign)
 from .grids import boundary_z_spacings, is_tripolar
 
 
@@ -176,11 +177,17 @@ def _groups(fields):
 def _check_supported(f):
     """Scope of this halo fill: the north Zipper (the reference's own code), Oceananigans' periodic x pass
     that must follow it, the latitude-band seams, the no-flux mirror of Flux-class south / bottom / top sides (the default
-    conditions of a model's Center fields) and the first-halo-point extrapolation of Value / Gradient south / bottom / top sides.  Every
-    other south / bottom / top condition (Open, unknown classes) and every non-periodic x condition is Oceananigans': a field that carries
-    one is refused loudly instead of being returned with stale halos."""
+    conditions of a model's Center fields), the first-halo-point extrapolation of Value / Gradient south / bottom / top sides and the face
+    write of an Open south side of a (Center, Face, Center) field and of Open bottom / top sides of a (Center, Center, Face) field (a
+    model's impenetrable v and w).  Every other south / bottom / top condition (Open at another location or with a function-valued
+    condition, unknown classes) and every non-periodic x condition is Oceananigans': a field that carries one is refused loudly instead of
+    being returned with stale halos."""
     from .boundary_conditions import HaloCommunication, Periodic
     bcs = f.boundary_conditions
+    for side in ("west", "east", "south", "north", "bottom", "top"):
+        bc = getattr(bcs, side)
+        if is_open(bc):
+            _check_open(f, side, bc)
     for side in ("west", "east"):
         bc = getattr(bcs, side)
         if bc is not None and not isinstance(bc.classification, Periodic):
@@ -188,16 +195,38 @@ def _check_supported(f):
                                       "(tripolar grids are Periodic in x)")
     for side in ("south", "north"):
         bc = getattr(bcs, side)
-        if bc is not None and not is_zipper(bc) and not isinstance(bc.classification, HaloCommunication) \
+        if bc is not None and not is_open(bc) and not is_zipper(bc) and not isinstance(bc.classification, HaloCommunication) \
                 and not (side == "south" and _bounded_class(bc)):
             raise NotImplementedError(f"fill_halo_regions: {side} boundary condition {bc.classification!r} is Oceananigans' to fill; "
-                                      "this library fills the Zipper north side, periodic x, the latitude-band seams and Flux, Value "
-                                      "and Gradient sides only")
+                                      "this library fills the Zipper north side, periodic x, the latitude-band seams, Flux, Value "
+                                      "and Gradient sides and the Open south face of a (Center, Face, Center) field only")
     for side in ("bottom", "top"):
         bc = getattr(bcs, side)
-        if bc is not None and not _bounded_class(bc):
+        if bc is not None and not _bounded_class(bc) and not is_open(bc):
             raise NotImplementedError(f"fill_halo_regions: {side} boundary condition {bc.classification!r} is Oceananigans' to fill; "
-                                      "this library fills Flux, Value and Gradient z halos only")
+                                      "this library fills Flux, Value and Gradient z halos and the Open bottom / top faces of a "
+                                      "(Center, Center, Face) field only")
+
+
+_OPEN_LOCATIONS = {"south": (Center, Face, Center), "bottom": (Center, Center, Face), "top": (Center, Center, Face)}
+
+
+def _check_open(f, side, bc):
+    """An Open side is filled where Oceananigans' models put one: south on a (Center, Face, Center) field, bottom / top on a
+    (Center, Center, Face) field, with a number, an array or None (impenetrable) as the normal velocity."""
+    at = "(" + ", ".join("Nothing" if L is None else L.__name__ for L in f.loc) + ")"
+    if f.loc != _OPEN_LOCATIONS.get(side):
+        raise NotImplementedError(f"fill_halo_regions: {side} boundary condition Open() on a field at {at} is not handled; this library "
+                                  "fills an Open south side of a (Center, Face, Center) field and Open bottom / top sides of a "
+                                  "(Center, Center, Face) field only")
+    if f.z_window is not None:
+        raise NotImplementedError(f"fill_halo_regions: {side} boundary condition Open() on a z-windowed field at {at} is not handled "
+                                  "(the window need not hold the boundary face)")
+    if callable(bc.condition):
+        sx = f.Nx + 2 * f.Hx
+        shape = (f.Nz, sx) if side == "south" else (f.Ny + 2 * f.Hy, sx)
+        raise NotImplementedError(f"fill_halo_regions: {side} boundary condition Open() on a field at {at} has a function-valued condition, "
+                                  f"which needs Oceananigans' clock; give a number, None or a {shape} array")
 
 
 def _bounded_class(bc):
@@ -242,6 +271,27 @@ def _condition(f, side, bc):
     got = f"a {tuple(c.shape)} tensor of {c.dtype} on {c.device}" if torch.is_tensor(c) else repr(c)
     raise ValueError(f"fill_halo_regions: {side} {bc.classification!r} condition must be {want}; got {got}"
                      + (" (function-valued conditions need Oceananigans' clock)" if callable(c) else ""))
+
+
+def _open_call(lib, fs, geom, ft, held):
+    """the tpg_fill_open_faces call of one geometry group (None if no field has an Open side): the pre-pass that writes the boundary face
+    of the group's Open south / bottom / top sides.  condition None (impenetrable) is the scalar 0; tensors read by pointer go to `held`."""
+    n = len(fs)
+    sides, values, conds = [0] * n, [0.0] * (3 * n), [None] * (3 * n)
+    bits = (_lib.TPG_SIDE_SOUTH, _lib.TPG_SIDE_BOTTOM, _lib.TPG_SIDE_TOP)
+    for fi, f in enumerate(fs):
+        for s, side in enumerate(_VG_SIDES):
+            bc = getattr(f.boundary_conditions, side)
+            if is_open(bc):
+                sides[fi] |= bits[s]
+                if bc.condition is not None:
+                    values[3 * fi + s], conds[3 * fi + s], t = _condition(f, side, bc)
+                    if t is not None:
+                        held.append(t)
+    if not any(sides):
+        return None
+    return (lib.tpg_fill_open_faces, (_lib.ptr_table([f.data for f in fs]), n, (C.c_uint8 * n)(*sides), (C.c_double * (3 * n))(*values),
+                                      (C.c_void_p * (3 * n))(*conds), *geom, ft))
 
 
 def _value_gradient_calls(lib, fs, geom, ft, held):
@@ -323,6 +373,8 @@ class HaloFillPlan:
     the same fields: calling the plan costs one C call per geometry group instead of ~10 us of Python.
 
     Order (pinned by test/test_zipper_boundary_conditions.jl:42-45):
+    the boundary faces of Open south / bottom / top sides, where a group has any (tpg_fill_open_faces: a local call, the first that
+    begin() issues on every path, so that the fold and the seam exchange carry what it writes) ->
     zipper fold on the north side (serial grid or last rank) -> periodic x (fills corners) ->
     on a distributed grid the y-seam exchange of Hy rows with the neighbour ranks -> the no-flux mirror of Flux-class south
     (serial grid or rank 0), bottom and top sides (tpg_fill_bounded_halos: one call per geometry group, after the horizontal fill
@@ -345,7 +397,7 @@ class HaloFillPlan:
         self._steps = []                      # (device, [(c function, argument tuple without the stream)], PendingExchange or None)
         self._keep = []                       # message buffers referenced by raw pointer from the argument tuples
         self._post = []                       # per step: calls that follow the host-driven seam exchange (run by finish())
-        self._held = []                       # Value / Gradient condition arrays and metrics, read by pointer at call time
+        self._held = []                       # Open / Value / Gradient condition arrays and metrics, read by pointer at call time
         lib = _lib.lib()
         for f in self.fields:
             if f.boundary_conditions is not None:
@@ -368,6 +420,10 @@ class HaloFillPlan:
             # Value / Gradient: south before the mirror, bottom / top after it (the order the fill is defined by)
             vg_south, vg_z = _value_gradient_calls(lib, fs, geom, ft, self._held)
             post_pass = [c for c in (vg_south, bounded, vg_z) if c is not None]
+            # Open faces: a local pre-pass, first on every path (the horizontal fill and the seam exchange carry what it writes)
+            open_faces = _open_call(lib, fs, geom, ft, self._held)
+            if open_faces is not None:
+                calls.append(open_faces)
             if comm is not None:
                 # EVERY rank of the chain enters the agreement, before it picks its branch: a rank whose fields are not uniformly zipped takes
                 # the host-driven branch below, and its peers must not be left waiting in the collective for it
