@@ -236,7 +236,7 @@ int tpg_fill_value_gradient_halos(void *const fields[], int nfields, int pass, c
  * k >= Nz+1 are not written.  A PRE-PASS: call it BEFORE the horizontal fill of the same fields (tpg_fill_halo_regions, tpg_zipper_fill
  * + tpg_periodic_x_fill, a tpg_fill_halo_regions_distributed* call, or the pack of a host-driven seam exchange), which folds the written
  * rows into the north halo, carries them into the x halos (overwriting the x-halo columns written here) and to the neighbour band; the
- * whole order is  Open faces -> horizontal fill (-> seam exchange) -> Value / Gradient south -> tpg_fill_bounded_halos -> Value /
+ * whole order is  (immersed mask ->) Open faces -> horizontal fill (-> seam exchange) -> Value / Gradient south -> tpg_fill_bounded_halos -> Value /
  * Gradient bottom / top.  The location is the caller's to check: this call writes the sides it is given.  Where one field has
  * TPG_SIDE_SOUTH and a z side, the cells both own (c[i, 1, 1], c[i, 1, Nz]) take the z side's value.
  * Unpinned: another reading of Oceananigans makes the same face write inside its regular south / bottom-top kernels; the two agree on
@@ -252,6 +252,41 @@ int tpg_fill_value_gradient_halos(void *const fields[], int nfields, int pass, c
  * TPG_SIDE_TOP on one field with Nz < 2 (one plane) and for a launch too large for 32-bit work-item indices. */
 int tpg_fill_open_faces(void *const fields[], int nfields, const uint8_t sides[], const double values[],
                         const void *const conditions[], int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
+
+/* ---- grid-fitted immersed boundary: column counts and the mask pass -----------------------------
+ * Oceananigans' ImmersedBoundaryGrid(grid, GridFittedBottom(bottom_height)) and mask_immersed_field!(field, value), which a model's
+ * update_state! runs on (u, v, w, T, S) immediately before fill_halo_regions! [recalled; parity unpinned -- Oceananigans' source is not at
+ * hand; the rule is stated here and in tests/immersed_ref.py].  The reference wraps every model grid this way ("We need a bottom height
+ * field that masks the singularities", examples/bickley_jet.jl:25-29; TRG, src/tripolar_grid.jl:371; test/test_zipper_boundary_conditions.jl:
+ * 47-54).  Grid Nz levels, z centres zc[1..Nz] strictly increasing, h[i, j] the bottom height at (Center, Center) AFTER its halo fill:
+ *     immersed_cell(i, j, k) = zc[k] <= h[i, j]   (the centre condition, compared in ft);   c[i, j] = #{k : zc[k] <= h[i, j]}, 0..Nz
+ *     inactive_cell = immersed_cell, or k < 1, or k > Nz, or j < 1 where the south side is a wall (serial grid, rank 0 of a band chain)
+ *     a node at (LX, LY, LZ) is peripheral if ANY cell of {i, i-1 if LX is Face} x {j, j-1 if LY is Face} x {k, k-1 if LZ is Face} is inactive
+ * x is periodic: cell i = 0 is read from h's filled west halo column; row j = 0 of a band that is not the southernmost from h's seam halo
+ * row.  No interior node touches a cell with j > Ny: the zipper enters only through h's own fill, which rewrites row Ny of h for i > Nx/2
+ * and so makes the mask mirror-symmetric there.  compute_numerical_bottom_height! of newer Oceananigans versions (it snaps the stored h to
+ * a cell face) does not change immersed_cell and is not built.
+ *
+ * tpg_immersed_column_counts: per horizontal location one dense Ny x Nx int32 plane over the interior (i fastest; any may be NULL):
+ *     n_cc = c   n_fc[i, j] = max(c[i, j], c[i-1, j])   n_cf[i, j] = max(c[i, j], c[i, j-1])   n_ff = max of the four,
+ * with c = Nz for j < 1 behind a south wall.  bottom_height: padded 2-D (Ny+2Hy) x (Nx+2Hx) of ft, halos filled; z_centers: Nz device
+ * values of ft (k = 1..Nz).  Computed once per grid; one launch.
+ *
+ * tpg_mask_immersed_fields: writes values[f] (a double holding an ft value) to every peripheral node i = 1..Nx, j = 1..Ny of field f and
+ * touches nothing else -- no halo cell, no unmasked cell; it never reads a field.  counts[f] is the count plane of the field's (x, y)
+ * location, zloc[f] its z location: a z-Center field is masked for k <= n, a z-Face field for k <= min(n + 1, Nzg), Nzg the GRID's level
+ * count.  The Nz ARGUMENT is the fields' own level count, as in every fill call: Nzg for z-Center fields, Nzg + 1 for z-Face fields, whose
+ * top level Nzg + 1 is therefore not visited (launch!(..., :xyz, ...) [recalled]).  A PRE-PASS of the halo fill, ahead of
+ * tpg_fill_open_faces:  mask -> Open faces -> horizontal fill -> ...  (an Open bottom value of w overwrites the mask's value at k = 1).  ONE launch per batch of up to TPG_MAX_FIELDS fields (more are split); Float32 and
+ * Float64, every halo width, every pointer aligned to the element type (count planes: to int32); capturable into a HIP graph.
+ * Every check precedes any launch: TPG_ERR_INVALID_ARGUMENT for a null table, plane, bottom_height or z_centers, a zloc other than
+ * TPG_CENTER / TPG_FACE, a pointer off its element alignment; TPG_ERR_UNSUPPORTED for more than 32-bit work items, for Hx < 1 where n_fc or
+ * n_ff is asked for and for Hy < 1 where n_cf or n_ff is asked for without a south wall. */
+int tpg_immersed_column_counts(const void *bottom_height, const void *z_centers, int south_is_wall,
+                               int32_t *n_cc, int32_t *n_fc, int32_t *n_cf, int32_t *n_ff,
+                               int Nx, int Ny, int Nz, int Hx, int Hy, int ft, void *stream);
+int tpg_mask_immersed_fields(void *const fields[], int nfields, const int32_t *const counts[], const int8_t zloc[],
+                             const double values[], int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
 
 /* ---- latitude-band halo exchange helpers (config 4) -------------------------------------
  * The interior seams of a y-slab partition exchange Hy full rows (all i incl. x halos, all

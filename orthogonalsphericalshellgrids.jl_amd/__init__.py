@@ -17,9 +17,9 @@ from .boundary_conditions import (BoundaryCondition, Center, Face, FieldBoundary
 from .grids import (CPU, GPU, convert_to_0_360, Distributed, Partition, OrthogonalSphericalShellGrid, R_Earth, Tripolar,
                     TripolarGrid, is_tripolar, local_row_range, local_sizes, reconstruct_global_grid, share_tables,
                     with_halo, x_domain, y_domain, RightConnected, FullyConnected, Bounded,
-                    PeriodicTopology)
+                    PeriodicTopology, GridFittedBottom, ImmersedBoundaryGrid)
 from .fields import (CenterField, Field, HaloFillPlan, XFaceField, YFaceField, ZFaceField, fill_halo_regions,
-                     halo_fill_plan, interior, set_)
+                     halo_fill_plan, interior, set_, immersed_mask_plan, mask_immersed_field)
 from .distributed import (LoopbackMailbox, PendingExchange, RcclComm, exchange_plan, exchange_y_halos, torch_distributed_transport)
 from .geometry import convert_to_latlong_frame, convert_to_native_frame, nonorthogonality_angle
 

@@ -76,6 +76,8 @@ SIGNATURES = {
     "tpg_fill_value_gradient_halos": (_i, [C.POINTER(_vp), _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(_vp), _vp,
                                            C.c_double, C.c_double] + _geom + [_i, _vp]),
     "tpg_fill_open_faces": (_i, [C.POINTER(_vp), _i, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(_vp)] + _geom + [_i, _vp]),
+    "tpg_immersed_column_counts": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "tpg_mask_immersed_fields": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(C.c_int8), C.POINTER(C.c_double)] + _geom + [_i, _vp]),
     "tpg_y_halo_buffer_elems": (_sz, [_i] * 6),
     "tpg_pack_y_halo": (_i, [C.POINTER(_vp), _i, _vp, _i] + _geom + [_i, _vp]),
     "tpg_unpack_y_halo": (_i, [C.POINTER(_vp), _i, _vp, _i] + _geom + [_i, _vp]),

@@ -8,7 +8,9 @@ one geometry into ONE zipper launch + one periodic-x launch, or into a single fu
 fields are small (tpg_fill_halo_regions); fields with no-flux south / bottom / top sides get one more launch after the horizontal
 fill (tpg_fill_bounded_halos); fields with Value / Gradient south / bottom / top sides get one launch before that mirror (south) and one after
 it (bottom / top): tpg_fill_value_gradient_halos; fields with Open (impenetrable) south / bottom / top sides -- a model's v and w -- get one
-launch BEFORE the horizontal fill, which writes the boundary face itself: tpg_fill_open_faces.
+launch BEFORE the horizontal fill, which writes the boundary face itself: tpg_fill_open_faces.  On an ImmersedBoundaryGrid,
+mask_immersed_field / immersed_mask_plan write a value to the peripheral nodes of the fields (tpg_mask_immersed_fields: a store-only pass over
+the masked cells), and halo_fill_plan(..., mask_immersed=value) puts that pass in front of the fill, as a model's update_state! orders them.
 """
 import ctypes as C
 import numbers
@@ -294,6 +296,25 @@ def _open_call(lib, fs, geom, ft, held):
                                       (C.c_void_p * (3 * n))(*conds), *geom, ft))
 
 
+def _mask_call(lib, fs, geom, ft, value, held):
+    """the tpg_mask_immersed_fields call of one geometry group (None on a grid without an immersed boundary: Oceananigans' method for such
+    a grid is a no-op): `value`, rounded once to the fields' type, goes to every peripheral node of the interior.  Reduced and z-windowed
+    fields are refused (Oceananigans masks a free surface with another rule, at k = Nz)."""
+    counts = getattr(fs[0].grid, "column_counts", None)
+    if counts is None:
+        return None
+    for f in fs:
+        if f.loc[2] is None or f.z_window is not None or None in f.loc[:2]:
+            raise NotImplementedError("mask_immersed_field: reduced and z-windowed fields are not handled "
+                                      "(Oceananigans masks a free-surface field with a different rule, at k = Nz)")
+    n = len(fs)
+    planes = [counts[("f" if f.loc[0] is Face else "c") + ("f" if f.loc[1] is Face else "c")] for f in fs]
+    held.extend(planes)
+    v = torch.tensor(value, dtype=fs[0].data.dtype).item()
+    return (lib.tpg_mask_immersed_fields, (_lib.ptr_table([f.data for f in fs]), n, _lib.ptr_table(planes),
+                                           (C.c_int8 * n)(*[_loc_code(f.loc[2]) for f in fs]), (C.c_double * n)(*([v] * n)), *geom, ft))
+
+
 def _value_gradient_calls(lib, fs, geom, ft, held):
     """(south call, bottom / top call) of tpg_fill_value_gradient_halos for one geometry group, None where no field has such a side; the
     tensors the calls read by pointer go to `held`.  The south spacing is dy_cf (Dy at (Center, Face), row j = 1) for every field location
@@ -373,6 +394,8 @@ class HaloFillPlan:
     the same fields: calling the plan costs one C call per geometry group instead of ~10 us of Python.
 
     Order (pinned by test/test_zipper_boundary_conditions.jl:42-45):
+    with `mask_immersed=value`, on an ImmersedBoundaryGrid, the immersed mask of the group (tpg_mask_immersed_fields), ahead of everything:
+    a model's update_state! masks its fields, then fills their halos [recalled], so an Open bottom value of w overwrites the mask's at k = 1 ->
     the boundary faces of Open south / bottom / top sides, where a group has any (tpg_fill_open_faces: a local call, the first that
     begin() issues on every path, so that the fold and the seam exchange carry what it writes) ->
     zipper fold on the north side (serial grid or last rank) -> periodic x (fills corners) ->
@@ -384,7 +407,7 @@ class HaloFillPlan:
     The plan holds the fields' tensors: it must be rebuilt if a field's `data` is replaced.
     """
 
-    def __init__(self, fields, *, exchange=None, pack_free=False, fields_per_stage=0):
+    def __init__(self, fields, *, exchange=None, pack_free=False, fields_per_stage=0, mask_immersed=None):
         if isinstance(fields, Field):
             fields = [fields]
         self.fields = list(fields)
@@ -420,7 +443,11 @@ class HaloFillPlan:
             # Value / Gradient: south before the mirror, bottom / top after it (the order the fill is defined by)
             vg_south, vg_z = _value_gradient_calls(lib, fs, geom, ft, self._held)
             post_pass = [c for c in (vg_south, bounded, vg_z) if c is not None]
-            # Open faces: a local pre-pass, first on every path (the horizontal fill and the seam exchange carry what it writes)
+            # the immersed mask, where asked for: ahead of everything, the Open faces included (an Open bottom value overwrites the mask's at k = 1)
+            mask = None if mask_immersed is None else _mask_call(lib, fs, geom, ft, mask_immersed, self._held)
+            if mask is not None:
+                calls.append(mask)
+            # Open faces: a local pre-pass, ahead of the horizontal fill on every path (the fill and the seam exchange carry what it writes)
             open_faces = _open_call(lib, fs, geom, ft, self._held)
             if open_faces is not None:
                 calls.append(open_faces)
@@ -529,8 +556,8 @@ def _run(device, calls):
                 _lib.check(fn(*args, stream, *(after[0] if after else ())))
 
 
-def halo_fill_plan(fields, *, exchange=None, pack_free=False, fields_per_stage=0):
-    return HaloFillPlan(fields, exchange=exchange, pack_free=pack_free, fields_per_stage=fields_per_stage)
+def halo_fill_plan(fields, *, exchange=None, pack_free=False, fields_per_stage=0, mask_immersed=None):
+    return HaloFillPlan(fields, exchange=exchange, pack_free=pack_free, fields_per_stage=fields_per_stage, mask_immersed=mask_immersed)
 
 
 def fill_halo_regions(fields, *, exchange=None):
@@ -540,3 +567,41 @@ def fill_halo_regions(fields, *, exchange=None):
     runs none.  Plans are not cached behind this function: a plan holds its fields, and a cache reachable from a field ties 32 GB tensors
     into a reference cycle that only the cycle collector frees (tried in round 6: the next test ran out of HBM)."""
     return HaloFillPlan(fields, exchange=exchange)()
+
+
+# -------------------------------------------------------------------------------------------------
+# mask_immersed_field!
+# -------------------------------------------------------------------------------------------------
+class ImmersedMaskPlan:
+    """mask_immersed_field!(field, value) for every field of `fields`, with the grouping by geometry and the pointer tables built once:
+    calling the plan issues one tpg_mask_immersed_fields call per geometry group on torch's current stream (capturable into a
+    torch.cuda.graph).  Writes `value` (rounded once to each group's type) to the peripheral nodes of the interior and nothing else; fields
+    on a grid without an immersed boundary are skipped.  The plan holds the fields' tensors and the grid's count planes."""
+
+    def __init__(self, fields, value=0):
+        if isinstance(fields, Field):
+            fields = [fields]
+        self.fields = list(fields)
+        self._held, self._steps = [], []
+        lib = _lib.lib()
+        groups = {}
+        for f in self.fields:
+            groups.setdefault((f.data.dtype, f.data.device, f.Nx, f.Ny, f.Nz, f.Hx, f.Hy, f.Hz, id(f.grid)), []).append(f)
+        for fs in groups.values():
+            f0 = fs[0]
+            call = _mask_call(lib, fs, (f0.Nx, f0.Ny, f0.Nz, f0.Hx, f0.Hy, f0.Hz), _lib.ft_of(f0.data.dtype), value, self._held)
+            if call is not None:
+                self._steps.append((f0.data.device, [call]))
+
+    def __call__(self):
+        for device, calls in self._steps:
+            _run(device, calls)
+
+
+def immersed_mask_plan(fields, value=0):
+    return ImmersedMaskPlan(fields, value)
+
+
+def mask_immersed_field(fields, value=0):
+    """mask_immersed_field!(field, value = 0) for one field or several: builds an ImmersedMaskPlan and runs it once"""
+    return ImmersedMaskPlan(fields, value)()

@@ -407,6 +407,9 @@ def with_halo(new_halo, old_grid):
     """with_halo(new_halo, grid)  (src/with_halo.jl:5-44): re-run the constructor from the stored
     Tripolar parameters with a different halo.  The old grid's 1-D tables are reused (TPG_BUILD_TABLES_VALID) when only Hx / Hz change;
     a new Hy -- or, distributed method, the default radius replacing a custom one -- changes the table key and recomputes them."""
+    if hasattr(old_grid, "underlying_grid"):
+        raise NotImplementedError("with_halo of an ImmersedBoundaryGrid is not provided: rebuild the underlying grid with the new halo and "
+                                  "wrap it again (the bottom height and its count planes are padded to the halo)")
     cm = old_grid.conformal_mapping
     kw = dict(z=old_grid.z_spec, halo=new_halo, north_poles_latitude=cm.north_poles_latitude,
               first_pole_longitude=cm.first_pole_longitude, southernmost_latitude=cm.southernmost_latitude,
@@ -426,3 +429,123 @@ def reconstruct_global_grid(grid):
                         north_poles_latitude=cm.north_poles_latitude,
                         first_pole_longitude=cm.first_pole_longitude,
                         southernmost_latitude=cm.southernmost_latitude)
+
+
+# ---------------------------------------------------------------------------------------------
+# immersed boundary
+# ---------------------------------------------------------------------------------------------
+class GridFittedBottom:
+    """GridFittedBottom(bottom_height) with Oceananigans' centre condition [recalled; parity unpinned]:
+    immersed_cell(i, j, k) = zc[k] <= bottom_height[i, j], compared in the grid's float type.  `bottom_height` is a number, a (Ny, Nx)
+    tensor / array, a callable f(λ, φ), or a reduced Field((Center, Center, None)) of the grid.  On an ImmersedBoundaryGrid it is that
+    Field with its halos filled.  compute_numerical_bottom_height! of newer Oceananigans versions (it snaps the stored height to a cell
+    face) does not change immersed_cell and is not built."""
+
+    def __init__(self, bottom_height):
+        import numbers
+        ok = (isinstance(bottom_height, numbers.Real) and not isinstance(bottom_height, bool)) or torch.is_tensor(bottom_height) \
+            or callable(bottom_height) or hasattr(bottom_height, "__array__") or _is_reduced_field(bottom_height)
+        if not ok:
+            raise TypeError("GridFittedBottom: bottom_height must be a number, a (Ny, Nx) tensor or array, a callable f(λ, φ) or a reduced "
+                            f"Field((Center, Center, None)); got {bottom_height!r}")
+        self.bottom_height = bottom_height
+
+    def __repr__(self):
+        return f"GridFittedBottom({self.bottom_height!r})"
+
+
+def _is_reduced_field(x):
+    return hasattr(x, "loc") and hasattr(x, "data") and hasattr(x, "boundary_conditions")
+
+
+class ImmersedBoundaryGrid:
+    """ImmersedBoundaryGrid(grid::TripolarGrid, GridFittedBottom(bottom_height)): what the reference wraps every model grid in ("We need a
+    bottom height field that masks the singularities", examples/bickley_jet.jl:25-29; TRG, src/tripolar_grid.jl:371).  Builds the reduced
+    bottom-height Field, set_s it, fills its halos through fill_halo_regions (zipper: row Ny comes out mirror-symmetric,
+    test/test_zipper_boundary_conditions.jl:47-54; periodic x; on a band grid the seam exchange, through `exchange`), then computes the
+    four column count planes with ONE tpg_immersed_column_counts call.  Exposes
+        underlying_grid, immersed_boundary.bottom_height (the filled Field), column_counts {"cc", "fc", "cf", "ff"} (int32, (Ny, Nx))
+    and forwards every other attribute to the underlying grid, so Field(loc, ibg), CenterField(ibg), ... and every halo-fill plan work
+    unchanged.  mask_immersed_field / halo_fill_plan(..., mask_immersed=value) consume the count planes (fields.py).
+    The constructor does all of this.  The one exception is a band (Distributed) grid with an explicit two-phase `exchange` transport
+    (post / wait, e.g. a LoopbackMailbox endpoint: several ranks emulated in one process): there the constructor posts the seam messages
+    of the bottom height and `finish()` -- called once on every rank's grid after all of them are built -- delivers them and computes the
+    count planes; `immersed_boundary` / `column_counts` raise until then.  No property read ever communicates or launches."""
+
+    def __init__(self, grid, ib, *, exchange=None):
+        if hasattr(grid, "underlying_grid") or not is_tripolar(grid):
+            raise TypeError("ImmersedBoundaryGrid: grid must be a (bare) TripolarGrid")
+        if not isinstance(ib, GridFittedBottom):
+            raise TypeError("ImmersedBoundaryGrid: only GridFittedBottom(bottom_height) is provided (partial cells and GridFittedBoundary "
+                            "masks are out of scope)")
+        zc = grid.z_centers[grid.Hz:grid.Hz + grid.Nz]
+        if grid.Nz > 1 and not bool((zc[1:] > zc[:-1]).all()):
+            raise ValueError("ImmersedBoundaryGrid: the z centres of the grid must be strictly increasing (the masked cells of a column "
+                             "are the levels k = 1 .. n)")
+        self.underlying_grid = grid
+        self._ib = self._counts = self._plan = None
+        from .boundary_conditions import Center
+        from .fields import Field, HaloFillPlan
+        h = ib.bottom_height
+        if _is_reduced_field(h):
+            if h.loc != (Center, Center, None) or getattr(h.grid, "underlying_grid", h.grid) is not grid or h.boundary_conditions is None:
+                raise ValueError("ImmersedBoundaryGrid: a bottom_height Field must be a Field((Center, Center, None)) of this grid with "
+                                 "boundary conditions")
+            field = h
+        else:
+            field = Field((Center, Center, None), self, name="bottom_height")
+            if callable(h):
+                field.set_(lambda lam, phi, z: h(lam, phi))
+            else:
+                import numbers
+                if not isinstance(h, numbers.Real):
+                    h = torch.as_tensor(h)
+                    if tuple(h.shape) != (grid.Ny, grid.Nx):
+                        raise ValueError(f"ImmersedBoundaryGrid: bottom_height must have shape (Ny, Nx) = {(grid.Ny, grid.Nx)}, got {tuple(h.shape)}")
+                field.set_(h)
+        self._bottom = field
+        self._plan = HaloFillPlan([field], exchange=exchange).begin()
+        if not (self._plan.is_distributed and hasattr(exchange, "post")):
+            self.finish()
+
+    def finish(self):
+        """delivery of the bottom height's seam rows and the count planes; the constructor calls it except with a two-phase `exchange`"""
+        if self._counts is not None:
+            return self
+        g, field = self.underlying_grid, self._bottom
+        self._plan.finish()
+        arch = g.architecture
+        wall = not (getattr(arch, "is_distributed", False) and arch.local_rank > 0)
+        device = field.data.device
+        with torch.cuda.device(device):
+            counts = {k: torch.empty((g.Ny, g.Nx), dtype=torch.int32, device=device) for k in ("cc", "fc", "cf", "ff")}
+            zc = g.z_centers[g.Hz:g.Hz + g.Nz].to(device=device, dtype=field.data.dtype).contiguous()
+            _lib.check(_lib.lib().tpg_immersed_column_counts(
+                field.data.data_ptr(), zc.data_ptr(), int(wall), *(counts[k].data_ptr() for k in ("cc", "fc", "cf", "ff")),
+                g.Nx, g.Ny, g.Nz, g.Hx, g.Hy, _lib.ft_of(field.data.dtype), _lib.current_stream_ptr(device)))
+            zc.record_stream(torch.cuda.current_stream(device))
+        self._ib = GridFittedBottom(field)
+        self._counts = counts
+        return self
+
+    def _finished(self, what):
+        if what is None:
+            raise RuntimeError("ImmersedBoundaryGrid: built with a two-phase exchange; call finish() once every rank's grid is built")
+        return what
+
+    @property
+    def immersed_boundary(self):
+        return self._finished(self._ib)
+
+    @property
+    def column_counts(self):
+        return self._finished(self._counts)
+
+    def __getattr__(self, name):
+        g = self.__dict__.get("underlying_grid")
+        if g is None or name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(g, name)
+
+    def __repr__(self):
+        return f"ImmersedBoundaryGrid({self.underlying_grid!r}, GridFittedBottom)"
