@@ -370,7 +370,15 @@ int tpg_halo_exchange_y_pipelined_peers(void *comm, int south_peer, int north_pe
  * other south / north side is neighbour communication): zipper fold (rank nranks-1) -> periodic x (merged / fused launch where
  * the geometry allows) -> tpg_halo_exchange_y, all enqueued on `stream`.  nranks = 1 is the serial fill (comm may be NULL).
  * xloc / yloc / sign are read on the zipper rank only.  Buffers as for tpg_halo_exchange_y (all NULL = pack-free).
- * The _peers form takes explicit neighbours (-1 = none) and the north side's kind, for hosts with their own rank map. */
+ * The _peers form takes explicit neighbours (-1 = none) and the north side's kind, for hosts with their own rank map.
+ * PRECONDITION on the band widths of a chain of more than one band (all four entry points below): the seam is ONE hop of Hy interior
+ * rows per side, after the fold, so EVERY band must own Ny >= Hy rows, and the LAST band Ny >= Hy + 1 when a field at y-Center is folded
+ * there (that fold reads rows Ny-Hy .. Ny-1: at Ny == Hy the first of them is the band's south halo row, not yet delivered).  A rank sees
+ * its own band only: Ny < Hy is refused by every fill (TPG_ERR_UNSUPPORTED, "halo larger than size"), and so is the zipper band with a
+ * south peer, Ny == Hy and a field with yloc = TPG_CENTER (TPG_ERR_UNSUPPORTED, before any launch or send) -- but only on the rank that
+ * is thin, at call time, while its neighbours may already wait in the exchange.  THE CALLER VOUCHES FOR THE NEIGHBOURS: check the widths
+ * of all ranks before the first fill (every rank knows the global Ny and the partition; the Python host does so at plan build,
+ * distributed.check_band_widths).  A chain of one band is the serial fill and keeps the reference's semantics at Ny == Hy. */
 int tpg_fill_halo_regions_distributed(void *comm, int rank, int nranks, void *const fields[], int nfields,
                                       const int8_t xloc[], const int8_t yloc[], const int32_t sign[],
                                       void *send_south, void *send_north, void *recv_south, void *recv_north,
@@ -380,7 +388,8 @@ int tpg_fill_halo_regions_distributed_peers(void *comm, int south_peer, int nort
                                             const int8_t xloc[], const int8_t yloc[], const int32_t sign[],
                                             void *send_south, void *send_north, void *recv_south, void *recv_north,
                                             int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
-/* The same whole fill with the seam exchange in its pipelined form (tpg_halo_exchange_y_pipelined above). */
+/* The same whole fill with the seam exchange in its pipelined form (tpg_halo_exchange_y_pipelined above); the same precondition on the
+ * band widths, refused in the same way. */
 int tpg_fill_halo_regions_distributed_pipelined(void *comm, int rank, int nranks, void *const fields[], int nfields,
                                                 const int8_t xloc[], const int8_t yloc[], const int32_t sign[],
                                                 void *send_south, void *send_north, void *recv_south, void *recv_north,

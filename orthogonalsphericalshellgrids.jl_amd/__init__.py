@@ -20,7 +20,8 @@ from .grids import (CPU, GPU, convert_to_0_360, Distributed, Partition, Orthogon
                     PeriodicTopology, GridFittedBottom, ImmersedBoundaryGrid)
 from .fields import (CenterField, Field, HaloFillPlan, XFaceField, YFaceField, ZFaceField, fill_halo_regions,
                      halo_fill_plan, interior, set_, immersed_mask_plan, mask_immersed_field)
-from .distributed import (LoopbackMailbox, PendingExchange, RcclComm, exchange_plan, exchange_y_halos, torch_distributed_transport)
+from .distributed import (LoopbackMailbox, PendingExchange, RcclComm, check_band_widths, exchange_plan, exchange_y_halos,
+                          torch_distributed_transport)
 from .geometry import convert_to_latlong_frame, convert_to_native_frame, nonorthogonality_angle
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

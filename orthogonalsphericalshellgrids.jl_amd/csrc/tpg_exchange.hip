@@ -204,7 +204,7 @@ static int peers_of(int rank, int nranks, Peers* p)
 }
 
 // what the two whole distributed fills check before the local fill
-static int distributed_fill_checks(int south_peer, int north_peer, int north_is_zipper, int nfields)
+static int distributed_fill_checks(int south_peer, int north_peer, int north_is_zipper, int nfields, const int8_t yloc[], int Ny, int Hy)
 {
     if (north_is_zipper && north_peer >= 0) {
         tpg::set_error("the north side is either the zipper or a seam, not both (north_peer %d)", north_peer);
@@ -214,6 +214,18 @@ static int distributed_fill_checks(int south_peer, int north_peer, int north_is_
         tpg::set_error("at most %d fields per distributed fill (one seam message per side)", TPG_MAX_FIELDS);
         return TPG_ERR_UNSUPPORTED;
     }
+    // The zipper band of a chain with Ny == Hy: the y-Center folds read rows Ny-Hy .. Ny-1 (zipper_boundary_condition.jl:95-99,128-132), and
+    // row 0 of this band is its south halo row, which the seam exchange -- AFTER the fold in this order -- has yet to deliver: the north halo
+    // would be folded from stale data.  Refused (the y-Face folds read rows 1 .. Ny and are right).  Ny < Hy is check_geom's refusal, in the
+    // local fill; a one-band chain (no south peer) is the serial fill, whose row 0 nobody delivers, and keeps the reference's semantics.
+    if (north_is_zipper && south_peer >= 0 && Hy > 0 && Ny == Hy && yloc)
+        for (int f = 0; f < nfields; ++f)
+            if (yloc[f] == TPG_CENTER) {
+                tpg::set_error("zipper band with a south seam: Ny = %d rows for a halo Hy = %d, and field %d is at y-Center -- its fold reads "
+                               "the band's south halo row before the seam has delivered it (the last band of a chain needs Ny >= Hy + 1)",
+                               Ny, Hy, f);
+                return TPG_ERR_UNSUPPORTED;
+            }
     return TPG_OK;
 }
 
@@ -408,7 +420,7 @@ int tpg_fill_halo_regions_distributed_peers(void* comm, int south_peer, int nort
                                             void* send_south, void* send_north, void* recv_south, void* recv_north,
                                             int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
-    int rc = distributed_fill_checks(south_peer, north_peer, north_is_zipper, nfields);
+    int rc = distributed_fill_checks(south_peer, north_peer, north_is_zipper, nfields, yloc, Ny, Hy);
     if (rc || (rc = tpg_fill_halo_regions(fields, nfields, xloc, yloc, sign, Nx, Ny, Nz, Hx, Hy, Hz, north_is_zipper ? 1 : 0, ft, stream))) return rc;
     if (south_peer < 0 && north_peer < 0) return TPG_OK;           // a one-band chain: the serial fill
     return tpg_halo_exchange_y_peers(comm, south_peer, north_peer, fields, nfields, send_south, send_north, recv_south, recv_north,
@@ -435,7 +447,7 @@ int tpg_fill_halo_regions_distributed_pipelined_peers(void* comm, int south_peer
                                                       int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft,
                                                       void* stream, void* comm_stream, int fields_per_stage)
 {
-    int rc = distributed_fill_checks(south_peer, north_peer, north_is_zipper, nfields);
+    int rc = distributed_fill_checks(south_peer, north_peer, north_is_zipper, nfields, yloc, Ny, Hy);
     if (rc || (rc = tpg_fill_halo_regions(fields, nfields, xloc, yloc, sign, Nx, Ny, Nz, Hx, Hy, Hz, north_is_zipper ? 1 : 0, ft, stream))) return rc;
     if (south_peer < 0 && north_peer < 0) return TPG_OK;
     return tpg_halo_exchange_y_pipelined_peers(comm, south_peer, north_peer, fields, nfields, send_south, send_north, recv_south, recv_north,

@@ -52,6 +52,31 @@ def exchange_plan(rank: int, nranks: int) -> List[SeamMessage]:
     return plan
 
 
+def check_band_widths(sizes, Hy, y_center_zipped):
+    """The band widths a latitude-band fill is right for; raises ValueError otherwise (a pure function: no device, no communication).
+    `sizes`: the interior rows of EVERY rank of the chain, rank 0 first (grids.local_sizes); `y_center_zipped`: the fields hold one at
+    y-Center, which the last rank folds.  A band fills in the order zipper (last rank) -> periodic x -> ONE seam hop of Hy interior rows
+    per side, so
+      * every band needs ny >= Hy: a thinner sender ships halo rows it has not received yet;
+      * the last band needs ny >= Hy + 1 for a y-Center fold: that fold reads rows Ny-Hy .. Ny-1 (zipper_boundary_condition.jl:95-99,
+        128-132), and with ny == Hy the first of them is the band's south halo row, which the seam delivers only afterwards.  The
+        y-Face folds read rows Ny-Hy+1 .. Ny and are right at ny == Hy.
+    Every rank holds the global size and the partition, hence the same `sizes`: all ranks raise the same error, and none is left
+    waiting in a collective or a seam.  A chain of one band is the serial fill and has no rule."""
+    sizes = [int(n) for n in sizes]
+    Hy = int(Hy)
+    if len(sizes) < 2 or Hy < 1:
+        return
+    for r, n in enumerate(sizes):
+        if n < Hy:
+            raise ValueError(f"latitude bands {sizes}: rank {r} owns {n} rows, fewer than the halo Hy = {Hy} (every band must own the "
+                             f"Hy rows it sends across a seam: ny >= Hy)")
+    if y_center_zipped and sizes[-1] < Hy + 1:
+        raise ValueError(f"latitude bands {sizes}: rank {len(sizes) - 1}, the zipper band, owns {sizes[-1]} rows for a halo Hy = {Hy}, and a "
+                         f"field at y-Center is folded there (its fold reads Hy rows below row Ny of the band's own interior: "
+                         f"ny >= Hy + 1 on the last band)")
+
+
 # -------------------------------------------------------------------------------------------------
 # transports
 # -------------------------------------------------------------------------------------------------

@@ -366,6 +366,21 @@ def _tables(fs):
     return (C.c_int8 * n)(*xl), (C.c_int8 * n)(*yl), (C.c_int32 * n)(*sg)
 
 
+def _check_band_widths(fs):
+    """distributed.check_band_widths for one geometry group on a latitude-band chain, from the widths of ALL ranks -- every rank holds the
+    global size and the partition, so every rank raises the same ValueError here, with no communication.  `y_center_zipped` is taken from
+    the locations, not from this rank's north condition (only the last rank carries the zipper; every rank must reach the same verdict).
+    A grid object that does not record its global size (assembled by hand, not by TripolarGrid) is the caller's to vouch for: the C entry
+    points still refuse what they can see of their own band."""
+    g = getattr(fs[0].grid, "underlying_grid", fs[0].grid)
+    arch = g.architecture
+    if not (getattr(arch, "is_distributed", False) and arch.ranks[1] > 1) or not g.global_size:
+        return
+    from .distributed import check_band_widths
+    from .grids import local_sizes
+    check_band_widths(local_sizes(g.global_size[1], arch.ranks[1], arch.partition.y_sizes), fs[0].Hy, any(f.loc[1] is Center for f in fs))
+
+
 def _agree_across_ranks(arch, value, what):
     """One collective at plan build: every rank of the chain must hold the same `value` (the stage layout of the seam exchange --
     group(k) of a rank pairs with group(k) of its neighbour, include/tripolar_hip.h).  Needs torch.distributed initialised over the
@@ -421,10 +436,12 @@ class HaloFillPlan:
         self._keep = []                       # message buffers referenced by raw pointer from the argument tuples
         self._post = []                       # per step: calls that follow the host-driven seam exchange (run by finish())
         self._held = []                       # Open / Value / Gradient condition arrays and metrics, read by pointer at call time
-        lib = _lib.lib()
         for f in self.fields:
             if f.boundary_conditions is not None:
                 _check_supported(f)
+        for fs in _groups(self.fields):
+            _check_band_widths(fs)            # every distributed group, ahead of the agreement collective and of any C call
+        lib = _lib.lib()
         for fs in _groups(self.fields):
             f0 = fs[0]
             g = getattr(f0.grid, "underlying_grid", f0.grid)

@@ -16,7 +16,8 @@ for t in range(trials):
     R = int(rng.integers(2, 7))
     Hx, Hy, Hz = int(rng.integers(1, 6)), int(rng.integers(1, 6)), int(rng.integers(0, 3))
     # local rows > halo: with ny == Hy the north rank's y-Center fold reads its own south HALO row, which the
-    # reference's order (zipper -> periodic x -> communication) has not received yet either
+    # reference's order (zipper -> periodic x -> communication) has not received yet either -- the plan refuses such a
+    # chain (distributed.check_band_widths: every band ny >= Hy, the last ny >= Hy + 1 with a y-Center field)
     ny = int(rng.integers(Hy + 1, Hy + 12)); Ny = ny * R
     Nx = 2 * int(rng.integers(max(1, Hx), 60)); Nz = int(rng.integers(1, 4))
     size, halo = (Nx, Ny, Nz), (Hx, Hy, Hz)
