@@ -411,7 +411,9 @@ int tpg_fill_halo_regions_distributed_pipelined_peers(void *comm, int south_peer
  * tpg_convert_frame: convert_to_latlong_frame (to_native = 0) / convert_to_native_frame (to_native = 1) of
  * examples/convert_to_latlong_frame.jl:12-55 for every interior (i, j, k): rotation of (u, v) by the local
  * direction cosines d1, d2 derived from phi_cf, phi_fc, dy_cc, dx_cc.  u, v, u_out, v_out: padded 3-D
- * (Center, Center, Center) parents (only the interior of the outputs is written; outputs may alias nothing). */
+ * (Center, Center, Center) parents (only the interior of the outputs is written; outputs may alias nothing).
+ * When Nx = 2 (mod 4) the two cells i = Nx/2, Nx/2 + 1 of row Ny sit on the grid's north pole, where dx_cc = 0: both
+ * conversions return NaN there (-deg2rad(0) / 0), exactly as the example's formula (:24) does; no other cell is affected. */
 int tpg_nonorthogonality_angle(const void *lambda_ff, const void *phi_ff, const uint8_t *immersed, double *angle,
                                int Nx, int Ny, int Hx, int Hy, int ft, void *stream);
 int tpg_convert_frame(const void *phi_cf, const void *phi_fc, const void *dy_cc, const void *dx_cc,

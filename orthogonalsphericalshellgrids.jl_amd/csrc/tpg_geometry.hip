@@ -73,6 +73,10 @@ template <> __device__ __forceinline__ float root<float>(float x) { return sqrtf
 struct FrameArgs { int Nx, Ny, Nz, Hx, Hy, Hz, sx; long long plane; int to_native; };
 constexpr int ZCH = 16;                                        // levels per thread of k_convert_frame
 
+// One column per thread: the form for rows that do not split into 16-B chunks (Nx % W != 0).  Only the Float32 instantiation can be reached:
+// that is Nx = 2 (mod 4); for Float64 W = 2 and Nx is always even (check_geom), so k_convert_frame<double> is instantiated by dispatch_ft
+// and never launched.
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_convert_frame(const T* __restrict__ phi_cf, const T* __restrict__ phi_fc,
                                                        const T* __restrict__ dy_cc, const T* __restrict__ dx_cc,
