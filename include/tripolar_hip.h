@@ -288,6 +288,55 @@ int tpg_immersed_column_counts(const void *bottom_height, const void *z_centers,
 int tpg_mask_immersed_fields(void *const fields[], int nfields, const int32_t *const counts[], const int8_t zloc[],
                              const double values[], int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
 
+/* ---- device reductions: field extrema and the advective CFL timescale ---------------------------
+ * What the reference's model drivers run between steps (examples/bickley_jet.jl:75,84,87; examples/distributed_bickley_jet.jl:77,92):
+ * maximum(u), maximum(v) in the progress callback and TimeStepWizard's cell_advection_timescale(model); and the six reductions of the metric
+ * arrays that the `show` of a grid prints (README.md:54-59 of the reference).  Min and max only: exact, independent of order, bit-reproducible.
+ * One pass over the interior rows (16-B chunks, element-aligned where rows or pointers are off the 16-B grid), one partial per block into
+ * `workspace`, then a second, tiny launch that reduces the partials and writes `out`: no float atomics, no inter-block flag or counter, no
+ * dependence on dispatch order.  Caller-owned device memory, asynchronous on `stream` (no host wait), capturable into a HIP graph; Float32
+ * and Float64, every halo width, every pointer aligned to its element type; every check precedes any launch.  `out` is DEVICE memory (doubles,
+ * 8-B aligned): the host reads it when it chooses.  On a latitude band the calls reduce the band's own rows; the MIN / MAX across ranks is
+ * the host's.
+ *
+ * tpg_reduce_workspace_bytes: an upper bound of the workspace either call needs for `nfields` fields of that geometry (the timescale
+ * call: nfields = 1); never 0; non-decreasing in every argument.  The workspace is 8-B aligned device memory; the calls write what they
+ * read of it first, so it needs no initialisation and may be shared by calls on ONE stream.
+ *
+ * tpg_field_extrema: for each of `nfields` fields of one geometry (up to TPG_MAX_FIELDS per launch; more are split), over the INTERIOR
+ * i = 1..Nx, j = 1..Ny, k = 1..Nz (Nz the fields' own level count: grid Nz + 1 for a z-Face field, whose top level is counted),
+ *     out[3f+0] = min c     out[3f+1] = max c     out[3f+2] = max |c|        values widened exactly to double
+ * No halo cell influences a result.  A NaN in a counted cell makes all three outputs of THAT field NaN (Julia's minimum / maximum, not
+ * fmin); the sign of a zero extremum is not specified.  An empty set gives +Inf, -Inf, -Inf.  counts may be NULL, and so may any counts[f]:
+ * every interior cell is counted.  Where counts[f] is given -- the count plane of the field's (x, y) location, tpg_immersed_column_counts --
+ * exactly the nodes that tpg_mask_immersed_fields writes for the same plane and zloc[f] are LEFT OUT: a z-Center field's k <= n, a z-Face
+ * field's k <= min(n + 1, Nzg), Nzg = Nz - 1 the grid's level count (zloc is read only where a plane is given, and may be NULL if counts is).
+ * The excluded set is [recalled], parity unpinned: Oceananigans' NotImmersed condition may differ on nodes that are peripheral only because
+ * of the domain's own walls (row 1 of v, level 1 of w); in a model those nodes hold the masked / impenetrable value anyway.
+ * With Nz = 1, Hz = 0 the call reduces padded 2-D arrays: the grid's metric arrays (minimum_xspacing, the grid summary).
+ *
+ * tpg_cell_advection_timescale: Oceananigans' cell_advection_timescale [recalled; parity unpinned -- the rule is stated here and in
+ * tests/reduction_ref.py].  For every interior cell i = 1..Nx, j = 1..Ny, k = 1..Nz, in the field type, left to right, no contraction:
+ *     s = |u[i,j,k]| / dx_fc[i,j] + |v[i,j,k]| / dy_cf[i,j] + |w[i,j,k]| / dz_f[k]        tau = 1 / s
+ *     out[0] = min tau, widened to double       NaN if any counted tau is NaN; +Inf if every s is 0 (or no cell is counted)
+ * u at (Face, Center, Center) and v at (Center, Face, Center) have Nz levels; w at (Center, Center, Face) has Nz + 1, its parent holds
+ * Nz + 1 + 2Hz planes of which levels 1..Nz are read.  dx_fc, dy_cf: the grid's padded 2-D metrics (Ny+2Hy) x (Nx+2Hx); dz_f: Nz device
+ * values for k = 1..Nz, the centre-to-centre spacing at face k; spacings are lengths (>= 0; a cell with a zero spacing and a zero
+ * velocity gives 0 / 0 = NaN, as the rule says).  n_cc: NULL, or the (Center, Center) count plane -- cells k <= n_cc[i,j] are left out.
+ * The kernel reduces max s and divides once: correctly rounded division is monotone, so 1 / max s == min (1 / s) bit for bit.
+ *
+ * TPG_ERR_INVALID_ARGUMENT for a null fields / out / velocity / spacing pointer, a counts table without a zloc table, a zloc other than
+ * TPG_CENTER / TPG_FACE, an unknown ft, a pointer off its element alignment (count planes: int32; out: double); TPG_ERR_UNSUPPORTED for
+ * more interior rows (Ny * Nz) than 32-bit work items index; TPG_ERR_WORKSPACE for a null, too small or misaligned workspace. */
+size_t tpg_reduce_workspace_bytes(int nfields, int Nx, int Ny, int Nz);
+int tpg_field_extrema(void *const fields[], int nfields, const int32_t *const counts[], const int8_t zloc[],
+                      double *out, void *workspace, size_t workspace_bytes,
+                      int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
+int tpg_cell_advection_timescale(const void *u, const void *v, const void *w,
+                                 const void *dx_fc, const void *dy_cf, const void *dz_f,
+                                 const int32_t *n_cc, double *out, void *workspace, size_t workspace_bytes,
+                                 int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
+
 /* ---- latitude-band halo exchange helpers (config 4) -------------------------------------
  * The interior seams of a y-slab partition exchange Hy full rows (all i incl. x halos, all
  * levels incl. z halos) per side and field; the transport (RCCL send/recv, ROCm-aware MPI) stays

@@ -23,5 +23,8 @@ from .fields import (CenterField, Field, HaloFillPlan, XFaceField, YFaceField, Z
 from .distributed import (LoopbackMailbox, PendingExchange, RcclComm, check_band_widths, exchange_plan, exchange_y_halos,
                           torch_distributed_transport)
 from .geometry import convert_to_latlong_frame, convert_to_native_frame, nonorthogonality_angle
+from .reductions import (AdvectionTimescalePlan, ExtremaPlan, TimeStepWizard, advection_timescale_plan, cell_advection_timescale,
+                         extrema_plan, field_extrema, grid_summary, maximum, minimum, minimum_xspacing, minimum_yspacing, summary,
+                         z_face_spacings)
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

@@ -78,6 +78,9 @@ SIGNATURES = {
     "tpg_fill_open_faces": (_i, [C.POINTER(_vp), _i, C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.POINTER(_vp)] + _geom + [_i, _vp]),
     "tpg_immersed_column_counts": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "tpg_mask_immersed_fields": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(C.c_int8), C.POINTER(C.c_double)] + _geom + [_i, _vp]),
+    "tpg_reduce_workspace_bytes": (_sz, [_i] * 4),
+    "tpg_field_extrema": (_i, [C.POINTER(_vp), _i, C.POINTER(_vp), C.POINTER(C.c_int8), _vp, _vp, _sz] + _geom + [_i, _vp]),
+    "tpg_cell_advection_timescale": (_i, [_vp] * 9 + [_sz] + _geom + [_i, _vp]),
     "tpg_y_halo_buffer_elems": (_sz, [_i] * 6),
     "tpg_pack_y_halo": (_i, [C.POINTER(_vp), _i, _vp, _i] + _geom + [_i, _vp]),
     "tpg_unpack_y_halo": (_i, [C.POINTER(_vp), _i, _vp, _i] + _geom + [_i, _vp]),
