@@ -41,6 +41,9 @@ class _LongDouble:
         return np.asarray(a).astype(np.longdouble)       # exact for Float32 / Float64
 
     sin, cos, sqrt, arccos = staticmethod(np.sin), staticmethod(np.cos), staticmethod(np.sqrt), staticmethod(np.arccos)
+    # the grid build's functions (tests/grid_ref.py)
+    tan, arctan, arcsin = staticmethod(np.tan), staticmethod(np.arctan), staticmethod(np.arcsin)
+    arcsinh, sinh, cosh = staticmethod(np.arcsinh), staticmethod(np.sinh), staticmethod(np.cosh)
 
     @staticmethod
     def div(a, b):
@@ -63,6 +66,8 @@ class _MPMath:
         self.sin, self.cos = f(_mp.sin), f(_mp.cos)
         self.sqrt = f(nan_safe(lambda x: _mp.sqrt(x) if x >= 0 else _mp.nan))
         self.arccos = f(nan_safe(lambda x: _mp.acos(x) if abs(x) <= 1 else _mp.nan))
+        self.tan, self.arctan, self.arcsinh, self.sinh, self.cosh = f(_mp.tan), f(_mp.atan), f(_mp.asinh), f(_mp.sinh), f(_mp.cosh)
+        self.arcsin = f(nan_safe(lambda x: _mp.asin(x) if abs(x) <= 1 else _mp.nan))
 
         def div(a, b):                                    # IEEE classes for x / 0, as the long-double path gives
             if _mp.isnan(a) or _mp.isnan(b):

@@ -34,6 +34,8 @@ CASES = [
     ("asinh", lambda: np.concatenate([RNG.uniform(0, 40, 200), 10.0 ** RNG.uniform(-8, 0, 100)]), mp.asinh, 0.501),
     ("sinh", lambda: np.concatenate([RNG.uniform(0, 5, 200), 10.0 ** RNG.uniform(-8, 0, 100)]), mp.sinh, 0.501),
     ("cosh", lambda: np.concatenate([RNG.uniform(0, 5, 200), 10.0 ** RNG.uniform(-8, 0, 100)]), mp.cosh, 0.501),
+    ("acos", lambda: np.concatenate([RNG.uniform(-1, 1, 600), 1 - 10.0 ** RNG.uniform(-16, -1, 200), -(1 - 10.0 ** RNG.uniform(-16, -1, 200)),
+                                     np.array([1.0, -1.0, 0.5, -0.5, 0.0])]), mp.acos, 1.0),
 ]
 
 

@@ -9,7 +9,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 N = 400_000
-SCALAR = {"sin": 0, "cos": 1, "sind": 2, "cosd": 3, "tand": 4, "atan": 5, "asin": 6, "asinh": 7, "sinh": 8, "cosh": 9}
+SCALAR = {"sin": 0, "cos": 1, "sind": 2, "cosd": 3, "tand": 4, "atan": 5, "asin": 6, "asinh": 7, "sinh": 8, "cosh": 9,
+          "acos": 10}                               # F_ACOS (csrc/tpg_probe.hip): acosD, used by the non-orthogonality angle kernel
 SPECIAL = np.array([0.0, -0.0, 1.0, -1.0, 0.5, -0.5, 45.0, -45.0, 90.0, -90.0, 135.0, 180.0, -180.0, 225.0, 270.0, 315.0,
                     359.99999999999994, 0.4375, 0.6875, 1.1875, 2.4375, 2.0 ** -27, 2.0 ** -26, 2.0 ** 66, 1e300,
                     np.inf, -np.inf, np.pi / 4, -np.pi / 4, np.nextafter(np.pi / 4, 1), np.pi / 2, np.pi, -np.pi,
@@ -43,6 +44,7 @@ def args_for(name, rng):
         "tand": [u(0, 89, N // 2)],
         "atan": [u(-5, 5, N), 10.0 ** u(-40, 40, N // 4) * rng.choice([-1, 1], N // 4)],
         "asin": [u(-1, 1, N), 10.0 ** u(-30, 0, N // 4), 1 - 10.0 ** u(-16, -1, 5000)],
+        "acos": [u(-1, 1, N), 1 - 10.0 ** u(-16, -1, 5000), -(1 - 10.0 ** u(-16, -1, 5000)), np.array([1.0, -1.0, 0.5, -0.5, 0.0])],
         "asinh": [u(0, 40, 20000), 10.0 ** u(-12, 1, 20000)],
         "sinh": [u(0, 6, 20000), 10.0 ** u(-12, 0, 20000)],
         "cosh": [u(0, 6, 20000), 10.0 ** u(-12, 0, 20000)],
@@ -52,7 +54,7 @@ def args_for(name, rng):
         sp = sp[np.abs(sp) < 1e6]
     if name in ("sind", "cosd"):
         sp = sp[np.isfinite(sp)]
-    if name == "asin":
+    if name in ("asin", "acos"):
         sp = sp[np.abs(sp) <= 1]
     return np.concatenate(parts + [sp])
 

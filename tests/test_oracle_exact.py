@@ -20,7 +20,8 @@ Two claims, tolerance as in BASELINE.json's north_star (1e-12 relative for Float
       conditioning.
 The cells are sampled away from the fold, the seam and the south edge so that only plain (i+-1, j+-1)
 neighbours enter; those index maps are pinned bit-exactly by the zipper tests and the identities in
-tests/test_oracle_kat.py.
+tests/test_oracle_kat.py.  The edge bound of 2.0 below holds AWAY from the 0 / 360 longitude wrap only: an edge across it has its haversine
+half-angle next to pi and reaches 2.4 in the same units -- tests/grid_ref.py derives the per-edge bound and checks whole arrays.
 """
 import mpmath as mp
 import numpy as np
