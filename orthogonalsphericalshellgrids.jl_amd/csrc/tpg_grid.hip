@@ -19,7 +19,10 @@
 //                                        and, after one barrier, every thread computes its cell from
 //                                        its own registers + LDS neighbours.  <= 128 VGPRs: 4
 //                                        waves/SIMD; transcendentals as straight-line batches
-//                                        (tpg_batch.hpp).
+//                                        (tpg_batch.hpp).  A wave's 64 columns are two strips of 32 that
+//                                        are lambda -> -lambda images of each other: the latitude / atan
+//                                        chain of a point is evaluated by one lane of the pair and handed
+//                                        to the other through LDS (points_pair).
 //                      0  k_cells        one thread per cell, everything recomputed: the simple
 //                                        reference form the tile kernel is checked against.
 //                    (Round 1 also carried two register-marching forms -- waves of 62 columns marching
@@ -443,63 +446,109 @@ __device__ __forceinline__ void points_fast(const GridK& g, const LaneConst& lc,
     s.X[1] = cs[2] * cs[3]; s.Y[1] = sn[2] * cs[3]; s.Z[1] = sn[3];      // FF
 }
 
-// same arithmetic in batches of 2 (for kernels that run 4 waves/SIMD and must stay under 128 VGPRs)
-__device__ __forceinline__ void points_fast2(const GridK& g, const LaneConst& lc, const RowTab& rt, Step4& s, const double* atab)
+// ---- the tile kernel's point set (the arithmetic of points_fast in batches of 2: 4 waves/SIMD, under 128 VGPRs): each chain of a lambda -> -lambda column pair is evaluated once ------------------------
+// A point's chain -- y / x, sqrt(y^2 + x^2), the two table atans, phi, cos(deg2rad phi) and, for CC / FF, sind / cosd(phi) --
+// depends on its column only through |a sind(lambda)| and |a cosd(lambda)|.  The lambda tables are num / N with an integer num,
+// and the column i' = 2 shift + 2 - i (Face), 2 shift + 1 - i (Center), mod Nx, has exactly -num: sind negates exactly, cosd is
+// unchanged, x' = -x, y' = y, and every later operation of the chain is sign-symmetric.  So |atan(y / x)|, phi, cos and the
+// latitude sine / cosine of the two columns are the same bits (tests/test_pair_premise.py; DESIGN.md 4 records why the fold
+// partner and i + Nx/2 must NOT be used: lambda +- 180 is not representable at Nx = 3600).
+// A wave holds two half-wave strips that are such images of each other (see k_cells_tile).  Lanes 0-31 evaluate the two Center-x
+// chains CC(jc), CF(jf) of their column and sind / cosd of CC's latitude, lanes 32-63 the two Face-x chains FC(jc), FF(jf) and
+// sind / cosd of FF's latitude; the code is the same, the half only selects the table entries.  Each lane parks its 8 doubles in
+// the wave's own rows of the tile's LDS (they hold the point records only later), row = 3 k + {at1, phi, ca} of point k and
+// 12.. = sind / cosd(phi) of CC, FF, and every lane reads the rows of all four points back: its own two from its own slot, the
+// other two from lane 63 - l (Center) or 64 - l (Face), the lane that holds the image column.  The exchange therefore is the
+// permutation into the slots k as well: no select and no cross-lane VALU.  LDS operations of one wave execute in order; the
+// wave-scope fences keep the compiler from moving accesses across the exchange.
+// Sign of at1: atan(y / x) carries sign(y) xor sign(x), for every finite pair (the zero-x patch to +-pi/2 included, which stays
+// with the owner).  The two Face columns lambda = -180 and 0 are their own images, x = -+0 there, so the receiver must not negate
+// blindly: every lane gives |at1| the sign of ITS OWN y / x.  The sign of a product is the xor of its factors' signs, cosh > 0
+// and sinh(psi) is wave-uniform, so that sign is sign(a sind) xor sign(a cosd) xor sign(sinh): integer work on the high words.
+// (Applied to a lane's own chains too, where it is the identity except on a zero at1, whose sign the next operation,
+// -180/pi at1 + (+-90), drops.)  a = deg2rad(phi) is recomputed by every lane.  Everything after the chain is points_fast's, per lane.
+template <int R>
+__device__ __forceinline__ void points_pair(const GridK& g, const LaneConst& lc, const RowTab& rt, Step4& s, const double* atab,
+                                            double (*L)[R][64], int p, int lane)
 {
-    const double shC = rt.shC, chC = rt.chC, shF = rt.shF, chF = rt.chF;
-    double x[4] = { lc.aslF * chC, lc.aslC * chC, lc.aslF * chF, lc.aslC * chF };          // :67
-    double y[4] = { lc.aclF * shC, lc.aclC * shC, lc.aclF * shF, lc.aclC * shF };          // :68
-    double q[4], rr[4], at1[4], at2[4];
-    // y / x through the unscaled division: both are products of finite table entries of moderate size (|x| is 0 on the two pole
-    // meridians, else >= ~1e-17; tests/test_gpu_math.py checks div_nr against IEEE on that range).  A zero denominator is the one case
-    // that needs IEEE semantics (y / +-0 = +-Inf, and atan(+-Inf) = +-pi/2): those lanes are patched after the table atan, which can
-    // then take the FINITE form for every lane (no clamp of the argument; a NaN from div_nr(y, 0) just flows through the discarded lane).
-    bool zerox = false;
+    const bool face = lane >= 32;
+    const double aslO = face ? lc.aslF : lc.aslC, aclO = face ? lc.aclF : lc.aclC;      // the x-location this lane evaluates
+    {
+        const double x[2] = { aslO * rt.chC, aslO * rt.chF };                               // :67  own chain 0: row jc, 1: row jf
+        const double y[2] = { aclO * rt.shC, aclO * rt.shF };                               // :68
+        double q[2], rr[2], at1[2], at2[2], phi[2], a[2], ca[2];
+        // y / x through the unscaled division: both are products of finite table entries of moderate size (|x| is 0 on the two pole
+        // meridians, else >= ~1e-17; tests/test_gpu_math.py checks div_nr against IEEE on that range).  A zero denominator is the one case
+        // that needs IEEE semantics (y / +-0 = +-Inf, and atan(+-Inf) = +-pi/2): those lanes are patched after the table atan, which can
+        // then take the FINITE form for every lane (no clamp of the argument; a NaN from div_nr(y, 0) just flows through the discarded lane).
+        bool zerox = false;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { q[k] = div_nr(y[k], x[k]); zerox |= x[k] == 0.0; rr[k] = sqrt_nr<true>(y[k] * y[k] + x[k] * x[k]);   /* > 0: no pole below row Ny */ }
+        for (int m = 0; m < 2; ++m) { q[m] = div_nr(y[m], x[m]); zerox |= x[m] == 0.0; rr[m] = sqrt_nr<true>(y[m] * y[m] + x[m] * x[m]);   /* > 0: no pole below row Ny */ }
+        tpgb::atan_tab_b<2, true>(q, at1, atab);
+        tpgb::atan_tab_b<2, true>(rr, at2, atab);
+        if (zerox) {
 #pragma unroll
-    for (int h = 0; h < 4; h += 2) {
-        double qa[2] = { q[h], q[h + 1] }, ra[2] = { rr[h], rr[h + 1] }, o1[2], o2[2];
-        tpgb::atan_tab_b<2, true>(qa, o1, atab);
-        tpgb::atan_tab_b<2, true>(ra, o2, atab);      // ra = sqrt(...) of finite table products
-        at1[h] = o1[0]; at1[h + 1] = o1[1]; at2[h] = o2[0]; at2[h + 1] = o2[1];
+            for (int m = 0; m < 2; ++m)
+                if (x[m] == 0.0) {
+                    // msun: atan(+-Inf) = +-(atanhi[3] + atanlo[3]) = +-pi/2 (the table row gives hi - ((-0 - lo) - t) = RN(hi + lo) = hi as well);
+                    // 0 / 0 stays NaN
+                    const double qq = y[m] / x[m];
+                    at1[m] = (qq != qq) ? qq : csign(kPio2Hi, qq);
+                }
+        }
+#pragma unroll
+        for (int m = 0; m < 2; ++m) { phi[m] = 90.0 - kC360Pi * at2[m]; a[m] = phi[m] * kDeg2Rad; }     // :78
+        if (tpgb::cos_lat_b<2>(a, ca)) { ca[0] = cosD(a[0]); ca[1] = cosD(a[1]); }
+        double lat[1] = { face ? phi[1] : phi[0] }, sp[1], cp[1];                          // FF(jf) | CC(jc)
+        if (tpgb::sincosd_lat_b<1>(lat, sp, cp)) tpgb::sincosd_b<1>(lat, sp, cp);
+        const int k0 = face ? 0 : 1;                                                       // point of chain 0; chain 1 is point k0 + 2
+        L[3 * k0 + 0][p][lane] = at1[0]; L[3 * k0 + 1][p][lane] = phi[0]; L[3 * k0 + 2][p][lane] = ca[0];
+        L[3 * k0 + 6][p][lane] = at1[1]; L[3 * k0 + 7][p][lane] = phi[1]; L[3 * k0 + 8][p][lane] = ca[1];
+        L[14 - 2 * k0][p][lane] = sp[0]; L[15 - 2 * k0][p][lane] = cp[0];                  // 12, 13: CC; 14, 15: FF
     }
-    if (zerox) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // lane 0 has no Face image (64 - 0); it is a west apron, whose Face points nobody reads: any finite chain will do
+    const int srcF = face ? lane : (lane == 0 ? 63 : 64 - lane), srcC = face ? 63 - lane : lane;
+    const int sgF = __double2hiint(lc.aslF) ^ __double2hiint(lc.aclF), sgC = __double2hiint(lc.aslC) ^ __double2hiint(lc.aclC);
+    const int sgJc = __double2hiint(rt.shC), sgJf = __double2hiint(rt.shF);
+    const int sg[4] = { sgF ^ sgJc, sgC ^ sgJc, sgF ^ sgJf, sgC ^ sgJf };
+    double at1[4], sp[2], cp[2];
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (x[k] == 0.0) {
-                // msun: atan(+-Inf) = +-(atanhi[3] + atanlo[3]) = +-pi/2 (the table row gives hi - ((-0 - lo) - t) = RN(hi + lo) = hi as well);
-                // 0 / 0 stays NaN
-                const double qq = y[k] / x[k];
-                at1[k] = (qq != qq) ? qq : csign(kPio2Hi, qq);
-            }
+    for (int k = 0; k < 4; ++k) {
+        const int src = (k == 0 || k == 2) ? srcF : srcC;
+        const double t = L[3 * k + 0][p][src];
+        at1[k] = __hiloint2double((__double2hiint(t) & 0x7fffffff) | (sg[k] & (int)0x80000000), __double2loint(t));
+        s.phi[k] = L[3 * k + 1][p][src];
+        s.ca[k] = L[3 * k + 2][p][src];
     }
+    sp[0] = L[12][p][srcC]; cp[0] = L[13][p][srcC];
+    sp[1] = L[14][p][srcF]; cp[1] = L[15][p][srcF];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();                                                       // the records go into these rows next
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         double l = -kC180Pi * at1[k];                          // :77 (no pole below row Ny)
-        s.phi[k] = 90.0 - kC360Pi * at2[k];                    // :78
         l += lc.hemi;                                          // :82
         l += g.fplp90;                                         // :86
         s.lam[k] = tpgb::fmod360_pos(tpgb::fmod360_small(l) + 360.0);     // :87
         s.a[k] = s.phi[k] * kDeg2Rad;
     }
-    double sn[4], cs[4];
-#pragma unroll
-    for (int h = 0; h < 4; h += 2) {
-        double aa[2] = { s.a[h], s.a[h + 1] }, cc2[2];
-        if (tpgb::cos_lat_b<2>(aa, cc2)) { cc2[0] = cosD(aa[0]); cc2[1] = cosD(aa[1]); }      // a = deg2rad(latitude)
-        s.ca[h] = cc2[0]; s.ca[h + 1] = cc2[1];
-    }
-    {   // unit vectors of CC (lam[1], phi[1]) and FF (lam[2], phi[2]): the two longitudes through the general form, the two latitudes
-        // through the |x| <= 90 form; sn / cs index = 2 * point + (0 longitude, 1 latitude)
-        double lon[2] = { s.lam[1], s.lam[2] }, lat[2] = { s.phi[1], s.phi[2] }, sl[2], cl[2], sp[2], cp[2];
-        tpgb::sincosd_b<2>(lon, sl, cl);
-        if (tpgb::sincosd_lat_b<2>(lat, sp, cp)) tpgb::sincosd_b<2>(lat, sp, cp);
-        sn[0] = sl[0]; cs[0] = cl[0]; sn[1] = sp[0]; cs[1] = cp[0];
-        sn[2] = sl[1]; cs[2] = cl[1]; sn[3] = sp[1]; cs[3] = cp[1];
-    }
-    s.X[0] = cs[0] * cs[1]; s.Y[0] = sn[0] * cs[1]; s.Z[0] = sn[1];      // CC
-    s.X[1] = cs[2] * cs[3]; s.Y[1] = sn[2] * cs[3]; s.Z[1] = sn[3];      // FF
+    double lon[2] = { s.lam[1], s.lam[2] }, sl[2], cl[2];
+    tpgb::sincosd_b<2>(lon, sl, cl);
+    s.X[0] = cl[0] * cp[0]; s.Y[0] = sl[0] * cp[0]; s.Z[0] = sp[0];      // CC
+    s.X[1] = cl[1] * cp[1]; s.Y[1] = sl[1] * cp[1]; s.Z[1] = sp[1];      // FF
+}
+
+// stored column of a strip lane, wrapped into 1..Nx (more than one period away only on grids narrower than a strip)
+__device__ __forceinline__ int wrap_col(int v, int Nx)
+{
+    if (v < 1) v += Nx;
+    if (v > Nx) v -= Nx;
+    if (v < 1 || v > Nx) { v = (v - 1) % Nx; v = (v < 0 ? v + Nx : v) + 1; }
+    return v;
 }
 
 // general rows (row Ny: fold, substitution, pole; row 0: zero south halo) through coord()
@@ -522,11 +571,18 @@ __device__ __noinline__ void points_general(const GridK& g, int i, int jc, int j
 // register state: a block of 64 x R threads evaluates one point set per thread (step s = FC(s), CC(s),
 // FF(s+1), CF(s+1)), parks {lambda, a, cos a[, X, Y, Z]} in LDS
 // (18 doubles x 64 x R), and after ONE barrier every thread with a south and east/west neighbour
-// inside the tile computes its cell from its own registers plus 48 LDS reads.  Row p = 0 and lanes
-// 0 / 63 are aprons (tiles overlap by one point row / two columns): (R-1)/R x 62/64 of the lanes emit;
-// the apron wave, which has no cell row, spends phase 2 on one of the eight haversines (Dy_ff) of all rows.
-// A wave owns one point row, so the special rows (0, Ny) are a wave-uniform branch to coord().
-// Same arithmetic as k_cells: bit-identical results.
+// inside the tile computes its cell from its own registers plus 48 LDS reads.  Row p = 0 is an apron (tiles
+// overlap by one point row); the apron wave, which has no cell row, spends phase 2 on one of the eight haversines
+// (Dy_ff) of all rows.
+// Columns: a wave holds TWO strips of 32 lanes.  With f1 = shift + 1 the stored column of lambda = -180, lanes 0-31 of
+// tile t hold the ascending columns f1 + 30 t - 1 + lane and lane 32 + k holds 2 shift + 1 - (column of lane 31 - k),
+// the x-Center lambda -> -lambda image, ascending as well; all wrapped into 1..Nx.  Lanes 0 / 32 are west aprons,
+// 31 / 63 east aprons, lanes 1-30 and 33-62 emit: (R-1)/R x 60/64 of the lanes.  The cells f1 .. f1 + Nx/2 - 1 and
+// their images partition 1..Nx, so tiles_x = ceil((Nx/2) / 30).  The Center image of lane l's column sits in lane
+// 63 - l and the Face image in lane 64 - l: phase 1 evaluates each pair's point chains once (points_pair).
+// A wave owns one point row, so the special rows (0, Ny) and |fplp90| > 360 are a wave-uniform branch to coord(),
+// unpaired: every lane evaluates its own column.
+// Same arithmetic as k_cells for every value: bit-identical results.
 template <int R> struct TileLds { double v[18][R][64]; };
 enum { L_FC = 0, L_CC = 3, L_FF = 9, L_CF = 15 };    // field bases: FC(lam,a,ca) CC(lam,a,ca,X,Y,Z) FF(6) CF(3)
 
@@ -598,9 +654,12 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
     const int tx = blockIdx.x;
     const int s0 = g.jm_lo - 1 + ty * (R - 1);
     const int s = s0 + p;                                                    // this wave's step
-    int i = tx * 62 + lane;
-    const bool col_emit = lane >= 1 && lane <= 62 && i <= g.Nx;
-    if (i > g.Nx + 1) i = g.Nx + 1;
+    // columns: lanes 0-31 ascend from shift + 30 tx (lane 1 of tile 0 is f1 = shift + 1, the column of lambda = -180), lanes 32-63 hold
+    // the Center images 2 shift + 1 - (column of lane 63 - l), ascending as well, so lane +- 1 is the east / west neighbour inside
+    // each half; all wrapped into 1..Nx, every lane evaluates a valid column.  The pair index kk < Nx / 2 guards a partial last tile.
+    const int hl = lane & 31;
+    const int i = wrap_col(lane >= 32 ? g.shift - 30 * tx - 30 + hl : g.shift + 30 * tx + hl, g.Nx);
+    const bool col_emit = hl >= 1 && hl <= 30 && 30 * tx + (lane >= 32 ? 30 - hl : hl - 1) < g.Nx / 2;
     const double Rad = g.R;
     const bool active_row = s <= g.jm_hi;                                    // rows past the band: idle waves
     const unsigned col = (unsigned)(i + g.Hx - 1);
@@ -612,12 +671,11 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
         const bool fast = s >= 1 && s < g.Ny && absD(g.fplp90) <= 360.0;     // wave-uniform
         if (fast) {
             LaneConst lc;
-            const int iw = i < 1 ? i + g.Nx : (i > g.Nx ? i - g.Nx : i);
-            int i0 = iw - g.shift; if (i0 < 1) i0 += g.Nx;
-            lc.aslF = g.ti[0 * g.Nx + iw - 1]; lc.aclF = g.ti[1 * g.Nx + iw - 1];
-            lc.aslC = g.ti[2 * g.Nx + iw - 1]; lc.aclC = g.ti[3 * g.Nx + iw - 1];
+            int i0 = i - g.shift; if (i0 < 1) i0 += g.Nx;
+            lc.aslF = g.ti[0 * g.Nx + i - 1]; lc.aclF = g.ti[1 * g.Nx + i - 1];
+            lc.aslC = g.ti[2 * g.Nx + i - 1]; lc.aclC = g.ti[3 * g.Nx + i - 1];
             lc.hemi = (i0 <= g.Nx / 2) ? -90.0 : 90.0;
-            points_fast2(g, lc, load_rowtab(g, s, s + 1), q, atab);
+            points_pair<R>(g, lc, load_rowtab(g, s, s + 1), q, atab, lds.v, p, lane);
         } else {
             Step4 tmp; GridK gc = g; points_general(gc, i, s, s + 1, tmp); q = tmp;
         }
@@ -859,7 +917,7 @@ int launch_build(const GridK& g, const OutPtrs& o, const HaloRegions& h, hipStre
     const bool south_in_band = g.jstart - g.Hy <= 1;
     const bool tile = cfg.cells_variant != 0 && tiles_y <= 65535 && offsets32;     // tile rows ride on gridDim.y; stores use 32-bit byte offsets
     if (tile) {
-        const int tiles_x = (g.Nx + 61) / 62;
+        const int tiles_x = (g.Nx / 2 + 29) / 30;                  // two strips of 30 emitting columns per wave: a lambda -> -lambda pair
         dim3 gridt((unsigned)tiles_x, (unsigned)tiles_y);
         if (nt) hipLaunchKernelGGL((k_cells_tile<T, true, R>), gridt, dim3(64 * R), 0, s, g, o, tiles_x);
         else    hipLaunchKernelGGL((k_cells_tile<T, false, R>), gridt, dim3(64 * R), 0, s, g, o, tiles_x);
