@@ -10,6 +10,7 @@
  * re-reads them; every setting gives identical results, tests/test_gpu_variants.py):
  *    TPG_CELLS_VARIANT        cell kernel of tpg_build_grid: 2 LDS tile (default, the product's form), 0 thread per cell (cross-check);
  *                             any other value selects 2
+ *    TPG_CELLS_ORDER          1 k_cells_tile's blocks take their tiles in the XCD-grouped order (default, the product's), 0 block id = tile (cross-check, A/B)
  *    TPG_BUILD_NT             1 streaming stores in tpg_build_grid (default), 0 plain stores
  *    TPG_ZIPPER_VARIANT       3 column work items (default), 0 row work items (the fallback kernels, everywhere)
  *    TPG_FILL_FUSED           0 never / 1 always (where valid) use the fused small-field fill; 2 = always, in its one-thread-per-cell form

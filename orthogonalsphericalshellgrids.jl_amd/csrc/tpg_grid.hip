@@ -14,7 +14,8 @@
 //                    then the 8 haversine edge lengths, 2 spherical quadrilateral areas and 2
 //                    product areas; stores 8 + 12 values.  Two forms with identical arithmetic
 //                    (tests/test_gpu_variants.py), selected by TPG_CELLS_VARIANT:
-//                      2  k_cells_tile   DEFAULT, the product's only form.  A block of 8 waves evaluates 8 point rows x 64
+//                      2  k_cells_tile   DEFAULT, the product's only form (blocks take their tiles in an XCD-grouped order, see
+//                                        tile_of_block).  A block of 8 waves evaluates 8 point rows x 64
 //                                        columns once (one point set per thread), parks them in LDS
 //                                        and, after one barrier, every thread computes its cell from
 //                                        its own registers + LDS neighbours.  <= 128 VGPRs: 4
@@ -633,8 +634,33 @@ __device__ __forceinline__ void hav_batch(const Nb (&X)[N], const Nb (&Y)[N], do
     for (int e = 0; e < N; ++e) d[e] = (2 * Rad) * as[e];      // 2 (R asin) = (2 R) asin bit for bit: doubling is exact (2 R: wave-uniform)
 }
 
+// ---- tile order ------------------------------------------------------------------------------------------------------------------
+// The launch is 1-D: block id -> tile through tile_of_block, tiles counted tx fastest, tile rows NORTH to SOUTH.  Consecutive block ids
+// land on different XCDs (id mod 8), so in the plain order the 128-B line that the strips of tiles tx and tx + 1 share is written from
+// two different L2s, and a partial-line write costs what a whole line costs.  The store stream, not the arithmetic, sets the kernel's
+// floor at sustained clocks (profiles/cells_floor: the kernel with its arithmetic removed takes 97 % of the full kernel's time), so
+// the order hands every XCD runs of 8 adjacent tiles: the shared lines meet in one L2.  (The persistent tile loop measured there is
+// not in the tree: slower by 8 %.)
+#ifndef TPG_CELLS_PROBE
+#define TPG_CELLS_PROBE 0      // instruments of profiles/cells_floor (scratch builds only: make GRID_FLAGS=-DTPG_CELLS_PROBE=n): 1 store-only,
+#endif                         // 2 compute-only (values folded, one store per lane), 3 = 2 without the table loads; results are WRONG by design
+#if TPG_CELLS_PROBE == 2 || TPG_CELLS_PROBE == 3
+#define TPG_EMIT(A, OFF, V) (fold ^= (unsigned long long)__double_as_longlong(V) + (A), fold_off = (OFF), folded = true)
+#else
+#define TPG_EMIT(A, OFF, V) put32<T, NT>(o, A, OFF, V)
+#endif
+
+// XCD-grouped order: a permutation inside every whole group of 64 block ids that gives the ids with one value of id mod 8 -- one XCD's
+// blocks -- 8 consecutive tiles; the ids of a last, partial group keep their own tile.  grouped = false: the identity (TPG_CELLS_ORDER 0)
+__device__ __forceinline__ int tile_of_block(int b, int tiles, bool grouped)
+{
+    const int base = b & ~63;
+    if (grouped && base + 64 <= tiles) return base + (b & 7) * 8 + ((b >> 3) & 7);
+    return b;
+}
+
 template <typename T, bool NT, int R>
-__global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, int tiles_x)
+__global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, int tiles_x, int tiles, int grouped)
 {
     __shared__ __attribute__((aligned(16))) double atabs[R][TPG_ATAN_TABLE_DOUBLES];
     __shared__ TileLds<R> lds;
@@ -647,35 +673,54 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // Tile rows are dispatched in blockIdx.y order: NORTH to SOUTH, so that the one slow row of a launch -- row Ny, whose wave takes the
+    // Tiles are counted tx fastest, tile rows NORTH to SOUTH, so that the one slow row of a launch -- row Ny, whose wave takes the
     // general (scalar) path through coord(): +2.2 us of block latency -- starts first instead of ending the launch.  Worth ~0.3 % at
     // 1/10 degree (in-process A/B, round 4: 505.7 -> 504.2 us per build, i.e. inside the noise); kept because it costs nothing.
-    const int ty = (int)gridDim.y - 1 - (int)blockIdx.y;
-    const int tx = blockIdx.x;
-    const int s0 = g.jm_lo - 1 + ty * (R - 1);
-    const int s = s0 + p;                                                    // this wave's step
+    const int tiles_y = tiles / tiles_x;
     // columns: lanes 0-31 ascend from shift + 30 tx (lane 1 of tile 0 is f1 = shift + 1, the column of lambda = -180), lanes 32-63 hold
     // the Center images 2 shift + 1 - (column of lane 63 - l), ascending as well, so lane +- 1 is the east / west neighbour inside
     // each half; all wrapped into 1..Nx, every lane evaluates a valid column.  The pair index kk < Nx / 2 guards a partial last tile.
     const int hl = lane & 31;
+    const double Rad = g.R;
+    const bool fast_grid = absD(g.fplp90) <= 360.0;
+#if TPG_CELLS_PROBE == 2 || TPG_CELLS_PROBE == 3
+    unsigned long long fold = 0; unsigned fold_off = 0; bool folded = false;
+#endif
+
+    const int t = tile_of_block((int)blockIdx.x, tiles, grouped != 0);
+    const int ty = tiles_y - 1 - t / tiles_x, tx = t % tiles_x;
+    const int s0 = g.jm_lo - 1 + ty * (R - 1);
+    const int s = s0 + p;                                                    // this wave's step
     const int i = wrap_col(lane >= 32 ? g.shift - 30 * tx - 30 + hl : g.shift + 30 * tx + hl, g.Nx);
     const bool col_emit = hl >= 1 && hl <= 30 && 30 * tx + (lane >= 32 ? 30 - hl : hl - 1) < g.Nx / 2;
-    const double Rad = g.R;
     const bool active_row = s <= g.jm_hi;                                    // rows past the band: idle waves
     const unsigned col = (unsigned)(i + g.Hx - 1);
     auto rowoff = [&](int j) -> unsigned { return (col + (unsigned)g.sx * (unsigned)(j - g.jstart + g.Hy)) * (unsigned)sizeof(T); };   // bytes
+    LaneConst lc;
+#if TPG_CELLS_PROBE == 3
+    const RowTab rt = RowTab{ 0.5 + 1e-3 * (s & 7), 1.1, 0.6, 1.2 };
+    lc.aslF = 0.31 + 0.01 * hl; lc.aclF = 0.72 + 1e-3 * (i & 1); lc.aslC = 0.33 + 0.01 * hl; lc.aclC = 0.74;
+#else
+    const RowTab rt = load_rowtab(g, s, s + 1);                              // clamped: loaded whether or not the wave takes the fast path
+    lc.aslF = g.ti[0 * g.Nx + i - 1]; lc.aclF = g.ti[1 * g.Nx + i - 1];      // every lane's column is a valid one
+    lc.aslC = g.ti[2 * g.Nx + i - 1]; lc.aclC = g.ti[3 * g.Nx + i - 1];
+#endif
 
     // ---- phase 1: one point set per thread
     Step4 q;
     if (active_row) {
-        const bool fast = s >= 1 && s < g.Ny && absD(g.fplp90) <= 360.0;     // wave-uniform
+        const bool fast = s >= 1 && s < g.Ny && fast_grid;                   // wave-uniform
         if (fast) {
-            LaneConst lc;
             int i0 = i - g.shift; if (i0 < 1) i0 += g.Nx;
-            lc.aslF = g.ti[0 * g.Nx + i - 1]; lc.aclF = g.ti[1 * g.Nx + i - 1];
-            lc.aslC = g.ti[2 * g.Nx + i - 1]; lc.aclC = g.ti[3 * g.Nx + i - 1];
             lc.hemi = (i0 <= g.Nx / 2) ? -90.0 : 90.0;
-            points_pair<R>(g, lc, load_rowtab(g, s, s + 1), q, atab, lds.v, p, lane);
+#if TPG_CELLS_PROBE == 1
+            const double pv = (lc.aslF + lc.aclC) * rt.shC + (double)(tx + lane);   // the table loads stay on the path
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { q.lam[k] = pv; q.phi[k] = pv; q.a[k] = pv; q.ca[k] = pv; }
+            q.X[0] = q.Y[0] = q.Z[0] = q.X[1] = q.Y[1] = q.Z[1] = pv;
+#else
+            points_pair<R>(g, lc, rt, q, atab, lds.v, p, lane);
+#endif
         } else {
             Step4 tmp; GridK gc = g; points_general(gc, i, s, s + 1, tmp); q = tmp;
         }
@@ -683,13 +728,13 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
         if (col_emit) {
             if (p >= 1 && s >= g.jm_lo) {
                 unsigned off = rowoff(s);
-                put32<T, NT>(o, TPG_LAMBDA_FC, off, q.lam[0]); put32<T, NT>(o, TPG_PHI_FC, off, q.phi[0]);
-                put32<T, NT>(o, TPG_LAMBDA_CC, off, q.lam[1]); put32<T, NT>(o, TPG_PHI_CC, off, q.phi[1]);
+                TPG_EMIT(TPG_LAMBDA_FC, off, q.lam[0]); TPG_EMIT(TPG_PHI_FC, off, q.phi[0]);
+                TPG_EMIT(TPG_LAMBDA_CC, off, q.lam[1]); TPG_EMIT(TPG_PHI_CC, off, q.phi[1]);
             }
             if ((p >= 1 || ty == 0) && s + 1 >= g.jm_lo && s + 1 <= g.jm_hi) {
                 unsigned off1 = rowoff(s + 1);
-                put32<T, NT>(o, TPG_LAMBDA_FF, off1, q.lam[2]); put32<T, NT>(o, TPG_PHI_FF, off1, q.phi[2]);
-                put32<T, NT>(o, TPG_LAMBDA_CF, off1, q.lam[3]); put32<T, NT>(o, TPG_PHI_CF, off1, q.phi[3]);
+                TPG_EMIT(TPG_LAMBDA_FF, off1, q.lam[2]); TPG_EMIT(TPG_PHI_FF, off1, q.phi[2]);
+                TPG_EMIT(TPG_LAMBDA_CF, off1, q.lam[3]); TPG_EMIT(TPG_PHI_CF, off1, q.phi[3]);
             }
         }
         double (*L)[R][64] = lds.v;
@@ -704,93 +749,110 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
     if (p == 0) {
         // The apron wave has no cell row of its own: instead of idling through phase 2 it computes one of the
         // eight haversines, Dy_ff = hav(FC(i,s), FC(i,s-1)), for every row of the tile from LDS (two rows at a time)
-        if (!col_emit) return;
-        double (*L)[R][64] = lds.v;
+        if (col_emit) {
+            double (*L)[R][64] = lds.v;
 #pragma unroll 1
-        for (int r = 1; r < R; r += 2) {
-            const int sa = s0 + r, sb = sa + 1;
-            if (sa > g.jm_hi) break;
-            const bool two = (r + 1 < R) && sb <= g.jm_hi;
-            const int rb = two ? r + 1 : r;
-            Nb X[2] = { Nb{ L[L_FC + 0][r][lane], L[L_FC + 1][r][lane], L[L_FC + 2][r][lane] },
-                        Nb{ L[L_FC + 0][rb][lane], L[L_FC + 1][rb][lane], L[L_FC + 2][rb][lane] } };
-            Nb Y[2] = { Nb{ L[L_FC + 0][r - 1][lane], L[L_FC + 1][r - 1][lane], L[L_FC + 2][r - 1][lane] },
-                        Nb{ L[L_FC + 0][rb - 1][lane], L[L_FC + 1][rb - 1][lane], L[L_FC + 2][rb - 1][lane] } };
+            for (int r = 1; r < R; r += 2) {
+                const int sa = s0 + r, sb = sa + 1;
+                if (sa > g.jm_hi) break;
+                const bool two = (r + 1 < R) && sb <= g.jm_hi;
+                const int rb = two ? r + 1 : r;
+                double dd2[2];
+#if TPG_CELLS_PROBE == 1
+                dd2[0] = dd2[1] = L[L_FC + 0][r][lane];
+#else
+                Nb X[2] = { Nb{ L[L_FC + 0][r][lane], L[L_FC + 1][r][lane], L[L_FC + 2][r][lane] },
+                            Nb{ L[L_FC + 0][rb][lane], L[L_FC + 1][rb][lane], L[L_FC + 2][rb][lane] } };
+                Nb Y[2] = { Nb{ L[L_FC + 0][r - 1][lane], L[L_FC + 1][r - 1][lane], L[L_FC + 2][r - 1][lane] },
+                            Nb{ L[L_FC + 0][rb - 1][lane], L[L_FC + 1][rb - 1][lane], L[L_FC + 2][rb - 1][lane] } };
+                hav_batch<2>(X, Y, Rad, dd2);
+#endif
+                if (sa >= g.jm_lo) TPG_EMIT(TPG_DY_FF, rowoff(sa), dd2[0]);
+                if (two && sb >= g.jm_lo) TPG_EMIT(TPG_DY_FF, rowoff(sb), dd2[1]);
+            }
+        }
+    } else if (active_row && s >= g.jm_lo) {                                 // idle rows have no phase 2 (wave-uniform)
+        if (col_emit) {                                                      // nor have apron lanes
+        // ---- phase 2: the cell (i, s) from own registers + LDS neighbours, loaded just in time so that the
+        //      live set stays under 128 VGPRs (4 waves/SIMD supply the ILP; batches of 2 suffice)
+        double (*L)[R][64] = lds.v;
+        const int pm = p - 1, le = lane + 1, lw = lane - 1;
+        const unsigned off = rowoff(s);
+        double d[8];
+#if TPG_CELLS_PROBE == 1
+        {
+            const double pv = q.lam[0] + L[L_FC + 0][pm][le];
+            TPG_EMIT(TPG_AZ_CC, off, pv); TPG_EMIT(TPG_AZ_FF, off, pv);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) d[k] = pv;
+        }
+#else
+        // 2 spherical quadrilaterals first (unit vectors only): Az_cc from FF points, Az_ff from CC points
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            V3 a, b, c, dd;
+            if (k == 0) {   // ffP = FF(i,s), ffEP = FF(i+1,s), ffE = FF(i+1,s+1), ff = FF(i,s+1)
+                a = V3{ L[L_FF + 3][pm][lane], L[L_FF + 4][pm][lane], L[L_FF + 5][pm][lane] };
+                b = V3{ L[L_FF + 3][pm][le], L[L_FF + 4][pm][le], L[L_FF + 5][pm][le] };
+                c = V3{ L[L_FF + 3][p][le], L[L_FF + 4][p][le], L[L_FF + 5][p][le] };
+                dd = V3{ q.X[1], q.Y[1], q.Z[1] };
+            } else {        // ccWP = CC(i-1,s-1), ccP = CC(i,s-1), cc = CC(i,s), ccW = CC(i-1,s)
+                a = V3{ L[L_CC + 3][pm][lw], L[L_CC + 4][pm][lw], L[L_CC + 5][pm][lw] };
+                b = V3{ L[L_CC + 3][pm][lane], L[L_CC + 4][pm][lane], L[L_CC + 5][pm][lane] };
+                c = V3{ q.X[0], q.Y[0], q.Z[0] };
+                dd = V3{ L[L_CC + 3][p][lw], L[L_CC + 4][p][lw], L[L_CC + 5][p][lw] };
+            }
+            double tt[4], at[4];
+            tt[0] = tri_tan_nr(a, b, c); tt[1] = tri_tan_nr(a, b, dd);
+            tt[2] = tri_tan_nr(a, c, dd); tt[3] = tri_tan_nr(b, c, dd);
+            if (__any(tpgb::atan_small_b<4>(tt, at))) {                 // wave-uniform fallback (large or degenerate triangles)
+                tt[0] = tri_tan(a, b, c); tt[1] = tri_tan(a, b, dd); tt[2] = tri_tan(a, c, dd); tt[3] = tri_tan(b, c, dd);
+                tpgb::atan_b<4>(tt, at);
+            }
+            // (2 t0 + 2 t1 + 2 t2 + 2 t3) / 2, summed left to right, is t0 + t1 + t2 + t3 summed left to right: doubling and halving are
+            // exact and commute with every rounding (no overflow / underflow at these magnitudes) -- 5 multiplications less per quadrilateral
+            double A = at[0];
+            A += at[1];
+            A += at[2];
+            A += at[3];
+            TPG_EMIT(k == 0 ? TPG_AZ_CC : TPG_AZ_FF, off, A * (Rad * Rad));
+        }
+
+        // 8 haversines in pairs; operand e = (x point, y point), each {lam, a, ca}
+        //   0 dxcc(fcE,fc) 1 dxfc(cc,ccW) 2 dxcf(ffEP,ffP) 3 dxff(cfP,cfWP) 4 dycc(cf,cfP) 5 dyfc(ff,ffP) 6 dycf(cc,ccP) 7 dyff(fc,fcP)
+        auto ld = [&](int f, int pp, int ll) -> Nb { return Nb{ L[f + 0][pp][ll], L[f + 1][pp][ll], L[f + 2][pp][ll] }; };
+        const Nb own[4] = { Nb{ q.lam[0], q.a[0], q.ca[0] }, Nb{ q.lam[1], q.a[1], q.ca[1] },
+                            Nb{ q.lam[2], q.a[2], q.ca[2] }, Nb{ q.lam[3], q.a[3], q.ca[3] } };   // fc cc ff cf
+#pragma unroll
+        for (int hb = 0; hb < 6; hb += 2) {
+            Nb X[2], Y[2];
+            if (hb == 0)      { X[0] = ld(L_FC, p, le); Y[0] = own[0];            X[1] = own[1];            Y[1] = ld(L_CC, p, lw); }
+            else if (hb == 2) { X[0] = ld(L_FF, pm, le); Y[0] = ld(L_FF, pm, lane); X[1] = ld(L_CF, pm, lane); Y[1] = ld(L_CF, pm, lw); }
+            else              { X[0] = own[3];           Y[0] = ld(L_CF, pm, lane); X[1] = own[2];            Y[1] = ld(L_FF, pm, lane); }
             double dd2[2];
             hav_batch<2>(X, Y, Rad, dd2);
-            if (sa >= g.jm_lo) put32<T, NT>(o, TPG_DY_FF, rowoff(sa), dd2[0]);
-            if (two && sb >= g.jm_lo) put32<T, NT>(o, TPG_DY_FF, rowoff(sb), dd2[1]);
+            d[hb] = dd2[0]; d[hb + 1] = dd2[1];
         }
-        return;
-    }
-    if (!active_row || s < g.jm_lo || !col_emit) return;                    // idle rows and apron lanes are done
-
-    // ---- phase 2: the cell (i, s) from own registers + LDS neighbours, loaded just in time so that the
-    //      live set stays under 128 VGPRs (4 waves/SIMD supply the ILP; batches of 2 suffice)
-    double (*L)[R][64] = lds.v;
-    const int pm = p - 1, le = lane + 1, lw = lane - 1;
-    const unsigned off = rowoff(s);
-
-    // 2 spherical quadrilaterals first (unit vectors only): Az_cc from FF points, Az_ff from CC points
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        V3 a, b, c, dd;
-        if (k == 0) {   // ffP = FF(i,s), ffEP = FF(i+1,s), ffE = FF(i+1,s+1), ff = FF(i,s+1)
-            a = V3{ L[L_FF + 3][pm][lane], L[L_FF + 4][pm][lane], L[L_FF + 5][pm][lane] };
-            b = V3{ L[L_FF + 3][pm][le], L[L_FF + 4][pm][le], L[L_FF + 5][pm][le] };
-            c = V3{ L[L_FF + 3][p][le], L[L_FF + 4][p][le], L[L_FF + 5][p][le] };
-            dd = V3{ q.X[1], q.Y[1], q.Z[1] };
-        } else {        // ccWP = CC(i-1,s-1), ccP = CC(i,s-1), cc = CC(i,s), ccW = CC(i-1,s)
-            a = V3{ L[L_CC + 3][pm][lw], L[L_CC + 4][pm][lw], L[L_CC + 5][pm][lw] };
-            b = V3{ L[L_CC + 3][pm][lane], L[L_CC + 4][pm][lane], L[L_CC + 5][pm][lane] };
-            c = V3{ q.X[0], q.Y[0], q.Z[0] };
-            dd = V3{ L[L_CC + 3][p][lw], L[L_CC + 4][p][lw], L[L_CC + 5][p][lw] };
+        {   // Dy_cf here; Dy_ff is the apron wave's
+            Nb X[1] = { own[1] }, Y[1] = { ld(L_CC, pm, lane) };
+            double dd1[1];
+            hav_batch<1>(X, Y, Rad, dd1);
+            d[6] = dd1[0];
         }
-        double tt[4], at[4];
-        tt[0] = tri_tan_nr(a, b, c); tt[1] = tri_tan_nr(a, b, dd);
-        tt[2] = tri_tan_nr(a, c, dd); tt[3] = tri_tan_nr(b, c, dd);
-        if (__any(tpgb::atan_small_b<4>(tt, at))) {                 // wave-uniform fallback (large or degenerate triangles)
-            tt[0] = tri_tan(a, b, c); tt[1] = tri_tan(a, b, dd); tt[2] = tri_tan(a, c, dd); tt[3] = tri_tan(b, c, dd);
-            tpgb::atan_b<4>(tt, at);
+#endif
+        TPG_EMIT(TPG_DX_CC, off, d[0]); TPG_EMIT(TPG_DX_FC, off, d[1]);
+        TPG_EMIT(TPG_DX_CF, off, d[2]); TPG_EMIT(TPG_DX_FF, off, d[3]);
+        TPG_EMIT(TPG_DY_CC, off, d[4]); TPG_EMIT(TPG_DY_FC, off, d[5]);
+        TPG_EMIT(TPG_DY_CF, off, d[6]);
+        TPG_EMIT(TPG_AZ_FC, off, d[5] * d[1]);
+        TPG_EMIT(TPG_AZ_CF, off, d[6] * d[2]);
         }
-        // (2 t0 + 2 t1 + 2 t2 + 2 t3) / 2, summed left to right, is t0 + t1 + t2 + t3 summed left to right: doubling and halving are
-        // exact and commute with every rounding (no overflow / underflow at these magnitudes) -- 5 multiplications less per quadrilateral
-        double A = at[0];
-        A += at[1];
-        A += at[2];
-        A += at[3];
-        put32<T, NT>(o, k == 0 ? TPG_AZ_CC : TPG_AZ_FF, off, A * (Rad * Rad));
     }
-
-    // 8 haversines in pairs; operand e = (x point, y point), each {lam, a, ca}
-    //   0 dxcc(fcE,fc) 1 dxfc(cc,ccW) 2 dxcf(ffEP,ffP) 3 dxff(cfP,cfWP) 4 dycc(cf,cfP) 5 dyfc(ff,ffP) 6 dycf(cc,ccP) 7 dyff(fc,fcP)
-    auto ld = [&](int f, int pp, int ll) -> Nb { return Nb{ L[f + 0][pp][ll], L[f + 1][pp][ll], L[f + 2][pp][ll] }; };
-    const Nb own[4] = { Nb{ q.lam[0], q.a[0], q.ca[0] }, Nb{ q.lam[1], q.a[1], q.ca[1] },
-                        Nb{ q.lam[2], q.a[2], q.ca[2] }, Nb{ q.lam[3], q.a[3], q.ca[3] } };   // fc cc ff cf
-    double d[8];
-#pragma unroll
-    for (int hb = 0; hb < 6; hb += 2) {
-        Nb X[2], Y[2];
-        if (hb == 0)      { X[0] = ld(L_FC, p, le); Y[0] = own[0];            X[1] = own[1];            Y[1] = ld(L_CC, p, lw); }
-        else if (hb == 2) { X[0] = ld(L_FF, pm, le); Y[0] = ld(L_FF, pm, lane); X[1] = ld(L_CF, pm, lane); Y[1] = ld(L_CF, pm, lw); }
-        else              { X[0] = own[3];           Y[0] = ld(L_CF, pm, lane); X[1] = own[2];            Y[1] = ld(L_FF, pm, lane); }
-        double dd2[2];
-        hav_batch<2>(X, Y, Rad, dd2);
-        d[hb] = dd2[0]; d[hb + 1] = dd2[1];
-    }
-    {   // Dy_cf here; Dy_ff is the apron wave's
-        Nb X[1] = { own[1] }, Y[1] = { ld(L_CC, pm, lane) };
-        double dd1[1];
-        hav_batch<1>(X, Y, Rad, dd1);
-        d[6] = dd1[0];
-    }
-    put32<T, NT>(o, TPG_DX_CC, off, d[0]); put32<T, NT>(o, TPG_DX_FC, off, d[1]);
-    put32<T, NT>(o, TPG_DX_CF, off, d[2]); put32<T, NT>(o, TPG_DX_FF, off, d[3]);
-    put32<T, NT>(o, TPG_DY_CC, off, d[4]); put32<T, NT>(o, TPG_DY_FC, off, d[5]);
-    put32<T, NT>(o, TPG_DY_CF, off, d[6]);
-    put32<T, NT>(o, TPG_AZ_FC, off, d[5] * d[1]);
-    put32<T, NT>(o, TPG_AZ_CF, off, d[6] * d[2]);
+#if TPG_CELLS_PROBE == 2 || TPG_CELLS_PROBE == 3
+    if (folded) { put32<T, NT>(o, TPG_DX_CC, fold_off, __longlong_as_double((long long)fold)); folded = false; }
+#endif
 }
+#undef TPG_EMIT
 
 // ---- K2: halo cells of the 20 arrays ------------------------------------------------------------
 // x/y location of array q (order of enum tpg_array)
@@ -908,24 +970,25 @@ int launch_build(const GridK& g, const OutPtrs& o, const HaloRegions& h, hipStre
     dim3 grid1(((g.Nx + 255) / 256) * (g.jm_hi - g.jm_lo + 1));
     // knobs (tpg::config(), read once; test library): TPG_CELLS_VARIANT 2 = k_cells_tile + k_halos (default, and the product's only form),
     // 0 = k_cells (thread per cell) + k_halos -- the cross-check: tests/test_gpu_variants.py; TPG_BUILD_NT 1 = streaming stores (default), 0 = plain
+    // TPG_CELLS_ORDER 1 = XCD-grouped tile order (default, the product's), 0 = block id = tile (cross-check, A/B)
     const tpg::Config& cfg = tpg::config();
     const bool nt = cfg.build_nt;
+    int rc = TPG_OK;
     constexpr int R = 8;                                       // point rows per tile (16 = one block per CU: measured 25 % slower)
     const int nrows = g.jm_hi - g.jm_lo + 1;
     const int tiles_y = (nrows + (R - 1) - 1) / (R - 1);
     const bool offsets32 = (unsigned long long)g.sx * (unsigned long long)(g.jend - g.jstart + 1 + 2 * g.Hy) * sizeof(T) < (1ull << 32);
     const bool south_in_band = g.jstart - g.Hy <= 1;
-    const bool tile = cfg.cells_variant != 0 && tiles_y <= 65535 && offsets32;     // tile rows ride on gridDim.y; stores use 32-bit byte offsets
+    const bool tile = cfg.cells_variant != 0 && tiles_y <= 65535 && offsets32;     // the sizes that took the tile kernel when tile rows rode on gridDim.y; stores use 32-bit byte offsets
     if (tile) {
         const int tiles_x = (g.Nx / 2 + 29) / 30;                  // two strips of 30 emitting columns per wave: a lambda -> -lambda pair
-        dim3 gridt((unsigned)tiles_x, (unsigned)tiles_y);
-        if (nt) hipLaunchKernelGGL((k_cells_tile<T, true, R>), gridt, dim3(64 * R), 0, s, g, o, tiles_x);
-        else    hipLaunchKernelGGL((k_cells_tile<T, false, R>), gridt, dim3(64 * R), 0, s, g, o, tiles_x);
+        const int tiles = tiles_x * tiles_y;
+        if (nt) hipLaunchKernelGGL((k_cells_tile<T, true, R>), dim3((unsigned)tiles), dim3(64 * R), 0, s, g, o, tiles_x, tiles, cfg.cells_order);
+        else    hipLaunchKernelGGL((k_cells_tile<T, false, R>), dim3((unsigned)tiles), dim3(64 * R), 0, s, g, o, tiles_x, tiles, cfg.cells_order);
     }
     else if (nt) hipLaunchKernelGGL((k_cells<T, true>), grid1, dim3(256), 0, s, g, o);
     else         hipLaunchKernelGGL((k_cells<T, false>), grid1, dim3(256), 0, s, g, o);
-    int rc = tpg::launch_status("k_cells");
-    if (rc) return rc;
+    if ((rc = tpg::launch_status("k_cells"))) return rc;
     // K3 rides in the K2 launch unless the grid is so short that a north-fold source row or the row-Ny
     // substitution could be a continuation row (then K3 must run after K2, as in the reference's order)
     HaloRegions hm = h;
