@@ -26,5 +26,6 @@ from .geometry import convert_to_latlong_frame, convert_to_native_frame, nonorth
 from .reductions import (AdvectionTimescalePlan, ExtremaPlan, TimeStepWizard, advection_timescale_plan, cell_advection_timescale,
                          extrema_plan, field_extrema, grid_summary, maximum, minimum, minimum_xspacing, minimum_yspacing, summary,
                          z_face_spacings)
+from .operators import VerticalVorticityField, VorticityPlan, compute_, vertical_vorticity, vorticity_plan
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

@@ -104,7 +104,15 @@ SIGNATURES = {
     "tpg_convert_frame": (_i, [_vp] * 8 + [_i] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_operators.h declares (libtripolar_hip_operators.so: a library of its own beside the product's)
+OPERATORS_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_operators.so")
+OPERATOR_SIGNATURES = {
+    "tpg_operators_last_error": (C.c_char_p, []),
+    "tpg_vertical_vorticity": (_i, [_vp] * 7 + [C.c_double] + _geom + [_i, _vp]),
+}
+
 _lib = None
+_operators = None
 
 
 def bind(path, signatures):
@@ -127,6 +135,24 @@ def lib():
                 "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
         _lib = bind(LIB_PATH, SIGNATURES)
     return _lib
+
+
+def operators_lib():
+    """Load libtripolar_hip_operators.so; raise loudly if it has not been built: there is no torch fallback for an operator either."""
+    global _operators
+    if _operators is None:
+        if not os.path.exists(OPERATORS_LIB_PATH):
+            raise ImportError(
+                f"{OPERATORS_LIB_PATH} not found: the HIP extension is the only backend of this package. "
+                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
+        _operators = bind(OPERATORS_LIB_PATH, OPERATOR_SIGNATURES)
+    return _operators
+
+
+def check_operators(status):
+    if status != 0:
+        raise TripolarHipError(status, operators_lib().tpg_operators_last_error().decode("utf-8", "replace"))
 
 
 def check(status):

@@ -42,6 +42,7 @@ static const Config* read_config()
     c->cells_order = env_int("TPG_CELLS_ORDER", 1) == 0 ? 0 : 1;
     const char* lib = getenv("TPG_RCCL_LIBRARY");
     c->rccl_library = (lib && *lib) ? strdup(lib) : nullptr;
+    c->vorticity_levels = env_int("TPG_VORTICITY_LEVELS", 0) > 0 ? env_int("TPG_VORTICITY_LEVELS", 0) : 0;
     return c;
 }
 
@@ -59,7 +60,7 @@ const Config& config()
 // the product library has no knobs: one constant record, no environment access
 const Config& config()
 {
-    static const Config k{ 2, true, 3, -1, -1, false, -1, 1, nullptr };
+    static const Config k{ 2, true, 3, -1, -1, false, -1, 1, nullptr, 0 };
     return k;
 }
 #endif

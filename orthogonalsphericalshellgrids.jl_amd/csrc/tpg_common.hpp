@@ -61,6 +61,8 @@ struct Config {
     const char* rccl_library; // TPG_RCCL_LIBRARY  nullptr (default, and always in the product): bind librccl by its fixed names; a path: bind THAT
                               //                   library instead -- the test double tools/nccl_shim/libnccl_shim.so, so that the exchange code runs
                               //                   between several real processes on a one-GPU box (RCCL refuses two ranks on one device)
+    int vorticity_levels;     // TPG_VORTICITY_LEVELS  0 (default, and always in the product): the levels a work item of k_vertical_vorticity walks are the
+                              //                       product's (tpg_operators.hip); n > 0: n levels (1 = the level-outer order; A/B, cross-check)
 };
 const Config& config();
 

@@ -23,7 +23,10 @@ TEST_SIGNATURES = {
     "tpg_math_probe": (_i, [_i, _vp, _vp, _vp, C.c_longlong, _vp]),
 }
 
+OPERATORS_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_operators_test.so")      # libtripolar_hip_operators.so + tpg_reload_config and TPG_VORTICITY_LEVELS
+
 _handle = None
+_operators = None
 
 
 def lib():
@@ -33,6 +36,16 @@ def lib():
             raise ImportError(f"{LIB_PATH} not found: build it with `make -C orthogonalsphericalshellgrids.jl_amd/csrc`")
         _handle = product.bind(LIB_PATH, {**product.SIGNATURES, **TEST_SIGNATURES})
     return _handle
+
+
+def operators_lib():
+    """the test build of the operators library: the product's symbols + tpg_reload_config (the TPG_VORTICITY_LEVELS knob)"""
+    global _operators
+    if _operators is None:
+        if not os.path.exists(OPERATORS_LIB_PATH):
+            raise ImportError(f"{OPERATORS_LIB_PATH} not found: build it with `make -C orthogonalsphericalshellgrids.jl_amd/csrc`")
+        _operators = product.bind(OPERATORS_LIB_PATH, {**product.OPERATOR_SIGNATURES, "tpg_reload_config": (_i, [])})
+    return _operators
 
 
 def check(status):
