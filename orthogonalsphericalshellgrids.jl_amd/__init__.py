@@ -27,5 +27,7 @@ from .reductions import (AdvectionTimescalePlan, ExtremaPlan, TimeStepWizard, ad
                          extrema_plan, field_extrema, grid_summary, maximum, minimum, minimum_xspacing, minimum_yspacing, summary,
                          z_face_spacings)
 from .operators import VerticalVorticityField, VorticityPlan, compute_, vertical_vorticity, vorticity_plan
+from .continuity import (ContinuityPlan, HorizontalDivergenceField, compute_w_from_continuity, continuity_plan, horizontal_divergence,
+                         z_center_spacings)
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

@@ -111,8 +111,16 @@ OPERATOR_SIGNATURES = {
     "tpg_vertical_vorticity": (_i, [_vp] * 7 + [C.c_double] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_continuity.h declares (libtripolar_hip_continuity.so: the third library, no test build)
+CONTINUITY_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_continuity.so")
+CONTINUITY_SIGNATURES = {
+    "tpg_continuity_last_error": (C.c_char_p, []),
+    "tpg_w_from_continuity": (_i, [_vp] * 9 + [C.c_double] + _geom + [_i, _vp]),
+}
+
 _lib = None
 _operators = None
+_continuity = None
 
 
 def bind(path, signatures):
@@ -153,6 +161,24 @@ def operators_lib():
 def check_operators(status):
     if status != 0:
         raise TripolarHipError(status, operators_lib().tpg_operators_last_error().decode("utf-8", "replace"))
+
+
+def continuity_lib():
+    """Load libtripolar_hip_continuity.so; raise loudly if it has not been built: there is no torch fallback for this operator either."""
+    global _continuity
+    if _continuity is None:
+        if not os.path.exists(CONTINUITY_LIB_PATH):
+            raise ImportError(
+                f"{CONTINUITY_LIB_PATH} not found: the HIP extension is the only backend of this package. "
+                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
+        _continuity = bind(CONTINUITY_LIB_PATH, CONTINUITY_SIGNATURES)
+    return _continuity
+
+
+def check_continuity(status):
+    if status != 0:
+        raise TripolarHipError(status, continuity_lib().tpg_continuity_last_error().decode("utf-8", "replace"))
 
 
 def check(status):
