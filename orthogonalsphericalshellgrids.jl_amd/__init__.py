@@ -29,5 +29,7 @@ from .reductions import (AdvectionTimescalePlan, ExtremaPlan, TimeStepWizard, ad
 from .operators import VerticalVorticityField, VorticityPlan, compute_, vertical_vorticity, vorticity_plan
 from .continuity import (ContinuityPlan, HorizontalDivergenceField, compute_w_from_continuity, continuity_plan, horizontal_divergence,
                          z_center_spacings)
+from .barotropic import (BarotropicCorrectionPlan, BarotropicModePlan, barotropic_correction, barotropic_correction_plan,
+                         barotropic_mode_plan, column_depth_table, compute_barotropic_mode)
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

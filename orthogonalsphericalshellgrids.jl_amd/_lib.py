@@ -118,9 +118,18 @@ CONTINUITY_SIGNATURES = {
     "tpg_w_from_continuity": (_i, [_vp] * 9 + [C.c_double] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_barotropic.h declares (libtripolar_hip_barotropic.so: the fourth library, no test build)
+BAROTROPIC_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_barotropic.so")
+BAROTROPIC_SIGNATURES = {
+    "tpg_barotropic_last_error": (C.c_char_p, []),
+    "tpg_barotropic_mode": (_i, [_vp] * 5 + _geom + [_i, _i, _vp]),
+    "tpg_barotropic_correction": (_i, [_vp] * 9 + [C.c_double] + _geom + [_i, _i, _vp]),
+}
+
 _lib = None
 _operators = None
 _continuity = None
+_barotropic = None
 
 
 def bind(path, signatures):
@@ -179,6 +188,24 @@ def continuity_lib():
 def check_continuity(status):
     if status != 0:
         raise TripolarHipError(status, continuity_lib().tpg_continuity_last_error().decode("utf-8", "replace"))
+
+
+def barotropic_lib():
+    """Load libtripolar_hip_barotropic.so; raise loudly if it has not been built: there is no torch fallback for these passes either."""
+    global _barotropic
+    if _barotropic is None:
+        if not os.path.exists(BAROTROPIC_LIB_PATH):
+            raise ImportError(
+                f"{BAROTROPIC_LIB_PATH} not found: the HIP extension is the only backend of this package. "
+                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
+        _barotropic = bind(BAROTROPIC_LIB_PATH, BAROTROPIC_SIGNATURES)
+    return _barotropic
+
+
+def check_barotropic(status):
+    if status != 0:
+        raise TripolarHipError(status, barotropic_lib().tpg_barotropic_last_error().decode("utf-8", "replace"))
 
 
 def check(status):
