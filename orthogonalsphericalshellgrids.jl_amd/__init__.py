@@ -31,5 +31,6 @@ from .continuity import (ContinuityPlan, HorizontalDivergenceField, compute_w_fr
                          z_center_spacings)
 from .barotropic import (BarotropicCorrectionPlan, BarotropicModePlan, barotropic_correction, barotropic_correction_plan,
                          barotropic_mode_plan, column_depth_table, compute_barotropic_mode)
+from .free_surface import (SplitExplicitFreeSurface, SplitExplicitSubcyclePlan, split_explicit_subcycle_plan, split_explicit_substep)
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

@@ -126,10 +126,18 @@ BAROTROPIC_SIGNATURES = {
     "tpg_barotropic_correction": (_i, [_vp] * 9 + [C.c_double] + _geom + [_i, _i, _vp]),
 }
 
+# every symbol include/tripolar_hip_free_surface.h declares (libtripolar_hip_free_surface.so: the fifth library, no test build)
+FREE_SURFACE_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_free_surface.so")
+FREE_SURFACE_SIGNATURES = {
+    "tpg_free_surface_last_error": (C.c_char_p, []),
+    "tpg_free_surface_substep": (_i, [_vp] * 19 + [C.c_double] * 3 + [_i] * 6 + [_vp]),
+}
+
 _lib = None
 _operators = None
 _continuity = None
 _barotropic = None
+_free_surface = None
 
 
 def bind(path, signatures):
@@ -206,6 +214,24 @@ def barotropic_lib():
 def check_barotropic(status):
     if status != 0:
         raise TripolarHipError(status, barotropic_lib().tpg_barotropic_last_error().decode("utf-8", "replace"))
+
+
+def free_surface_lib():
+    """Load libtripolar_hip_free_surface.so; raise loudly if it has not been built: there is no torch fallback for the sub-step either."""
+    global _free_surface
+    if _free_surface is None:
+        if not os.path.exists(FREE_SURFACE_LIB_PATH):
+            raise ImportError(
+                f"{FREE_SURFACE_LIB_PATH} not found: the HIP extension is the only backend of this package. "
+                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
+        _free_surface = bind(FREE_SURFACE_LIB_PATH, FREE_SURFACE_SIGNATURES)
+    return _free_surface
+
+
+def check_free_surface(status):
+    if status != 0:
+        raise TripolarHipError(status, free_surface_lib().tpg_free_surface_last_error().decode("utf-8", "replace"))
 
 
 def check(status):

@@ -1,7 +1,7 @@
 """The two ends of a split-explicit free surface's sub-cycle on a TripolarGrid: the barotropic mode of the 3-D velocities before it and the
 velocity correction after it, before w is diagnosed from continuity.  The reference's drivers build
 HydrostaticFreeSurfaceModel(; grid, free_surface = SplitExplicitFreeSurface(grid; substeps = 30)) (examples/bickley_jet.jl:44-55); the
-sub-cycle between the two calls is the model's.
+sub-cycle between the two calls is free_surface.py's (SplitExplicitFreeSurface, split_explicit_subcycle_plan).
 
 Everything numeric is tpg_barotropic_mode / tpg_barotropic_correction (include/tripolar_hip_barotropic.h, libtripolar_hip_barotropic.so): one
 launch each over the interior columns, in the fields' type,
