@@ -1,7 +1,11 @@
-"""ctypes binding of libtripolar_hip.so (include/tripolar_hip.h).
+"""ctypes binding of libtripolar_hip.so (include/tripolar_hip.h) and of the four operator libraries beside it
+(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h).
 
-This is the ONLY compute backend of the package: if the shared library is missing or a call
+This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
+
+A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
+status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic and free_surface.
 """
 import ctypes as C
 import os
@@ -133,13 +137,6 @@ FREE_SURFACE_SIGNATURES = {
     "tpg_free_surface_substep": (_i, [_vp] * 19 + [C.c_double] * 3 + [_i] * 6 + [_vp]),
 }
 
-_lib = None
-_operators = None
-_continuity = None
-_barotropic = None
-_free_surface = None
-
-
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
     handle = C.CDLL(path)
@@ -149,94 +146,41 @@ def bind(path, signatures):
     return handle
 
 
-def lib():
-    """Load libtripolar_hip.so; raise loudly if it has not been built (python __graft_entry__.py)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(
-                f"{LIB_PATH} not found: the HIP extension is the only backend of this package. "
-                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
-        _lib = bind(LIB_PATH, SIGNATURES)
-    return _lib
+def _load(path, signatures):
+    """bind `path`; raise loudly if it has not been built (python __graft_entry__.py): no library of the package has a torch fallback"""
+    if not os.path.exists(path):
+        raise ImportError(
+            f"{path} not found: the HIP extension is the only backend of this package. "
+            "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
+    return bind(path, signatures)
 
 
-def operators_lib():
-    """Load libtripolar_hip_operators.so; raise loudly if it has not been built: there is no torch fallback for an operator either."""
-    global _operators
-    if _operators is None:
-        if not os.path.exists(OPERATORS_LIB_PATH):
-            raise ImportError(
-                f"{OPERATORS_LIB_PATH} not found: the HIP extension is the only backend of this package. "
-                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
-        _operators = bind(OPERATORS_LIB_PATH, OPERATOR_SIGNATURES)
-    return _operators
+def _library(handle, path, signatures, last_error):
+    """(loader, checker) of one library.  `handle` and `path` NAME module-level variables, read at every call: the cached handle (None: not
+    loaded yet; tools.testlib swaps _lib) and the path, which a caller may assign before the first load.  `last_error`: its error channel."""
+    g = globals()
+    g.setdefault(handle, None)
+
+    def load():
+        if g[handle] is None:
+            g[handle] = _load(g[path], signatures)
+        return g[handle]
+
+    def check(status):
+        if status != 0:
+            raise TripolarHipError(status, getattr(load(), last_error)().decode("utf-8", "replace"))
+
+    load.__doc__ = f"Load the library at {path} (once); ImportError if it has not been built."
+    return load, check
 
 
-def check_operators(status):
-    if status != 0:
-        raise TripolarHipError(status, operators_lib().tpg_operators_last_error().decode("utf-8", "replace"))
-
-
-def continuity_lib():
-    """Load libtripolar_hip_continuity.so; raise loudly if it has not been built: there is no torch fallback for this operator either."""
-    global _continuity
-    if _continuity is None:
-        if not os.path.exists(CONTINUITY_LIB_PATH):
-            raise ImportError(
-                f"{CONTINUITY_LIB_PATH} not found: the HIP extension is the only backend of this package. "
-                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
-        _continuity = bind(CONTINUITY_LIB_PATH, CONTINUITY_SIGNATURES)
-    return _continuity
-
-
-def check_continuity(status):
-    if status != 0:
-        raise TripolarHipError(status, continuity_lib().tpg_continuity_last_error().decode("utf-8", "replace"))
-
-
-def barotropic_lib():
-    """Load libtripolar_hip_barotropic.so; raise loudly if it has not been built: there is no torch fallback for these passes either."""
-    global _barotropic
-    if _barotropic is None:
-        if not os.path.exists(BAROTROPIC_LIB_PATH):
-            raise ImportError(
-                f"{BAROTROPIC_LIB_PATH} not found: the HIP extension is the only backend of this package. "
-                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
-        _barotropic = bind(BAROTROPIC_LIB_PATH, BAROTROPIC_SIGNATURES)
-    return _barotropic
-
-
-def check_barotropic(status):
-    if status != 0:
-        raise TripolarHipError(status, barotropic_lib().tpg_barotropic_last_error().decode("utf-8", "replace"))
-
-
-def free_surface_lib():
-    """Load libtripolar_hip_free_surface.so; raise loudly if it has not been built: there is no torch fallback for the sub-step either."""
-    global _free_surface
-    if _free_surface is None:
-        if not os.path.exists(FREE_SURFACE_LIB_PATH):
-            raise ImportError(
-                f"{FREE_SURFACE_LIB_PATH} not found: the HIP extension is the only backend of this package. "
-                "Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(or `make -C orthogonalsphericalshellgrids.jl_amd/csrc`).")
-        _free_surface = bind(FREE_SURFACE_LIB_PATH, FREE_SURFACE_SIGNATURES)
-    return _free_surface
-
-
-def check_free_surface(status):
-    if status != 0:
-        raise TripolarHipError(status, free_surface_lib().tpg_free_surface_last_error().decode("utf-8", "replace"))
-
-
-def check(status):
-    if status != 0:
-        raise TripolarHipError(status, lib().tpg_last_error().decode("utf-8", "replace"))
+lib, check = _library("_lib", "LIB_PATH", SIGNATURES, "tpg_last_error")
+operators_lib, check_operators = _library("_operators", "OPERATORS_LIB_PATH", OPERATOR_SIGNATURES, "tpg_operators_last_error")
+continuity_lib, check_continuity = _library("_continuity", "CONTINUITY_LIB_PATH", CONTINUITY_SIGNATURES, "tpg_continuity_last_error")
+barotropic_lib, check_barotropic = _library("_barotropic", "BAROTROPIC_LIB_PATH", BAROTROPIC_SIGNATURES, "tpg_barotropic_last_error")
+free_surface_lib, check_free_surface = _library("_free_surface", "FREE_SURFACE_LIB_PATH", FREE_SURFACE_SIGNATURES, "tpg_free_surface_last_error")
+OPERATOR_LIBRARIES = (operators_lib, continuity_lib, barotropic_lib, free_surface_lib)
 
 
 def ft_of(dtype):

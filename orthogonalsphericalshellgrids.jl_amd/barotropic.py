@@ -16,11 +16,11 @@ of u and v inside the same launch.  The plan forms hold their tensors: calling o
 import torch
 
 from . import _lib
+from ._operator_plan import OperatorPlan, _check_fields, _ptr, _require
 from .boundary_conditions import Center, Face
-from .continuity import _dz_c
-from .fields import Field, HaloFillPlan
+from .fields import Field
 from .grids import is_tripolar
-from .reductions import _bare
+from .reductions import _bare, _grid_table, _z_spec_values, z_center_spacings
 
 _LOCS = {"u": (Face, Center, Center), "v": (Center, Face, Center),
          "U": (Face, Center, None), "V": (Center, Face, None), "Ubar": (Face, Center, None), "Vbar": (Center, Face, None)}
@@ -35,7 +35,7 @@ def column_depth_table(grid, dtype=None):
     columns' counts, which gives Oceananigans' min of the two depths.  Parity unpinned, like every operator.]"""
     g = _bare(grid)
     Nz = g.Nz
-    zz = g.z_spec.flatten().tolist() if torch.is_tensor(g.z_spec) else list(g.z_spec)
+    zz = _z_spec_values(g)
     if len(zz) == 2:
         z0, z1 = float(zz[0]), float(zz[1])
         faces = [z0 + (z1 - z0) * n / Nz for n in range(Nz)] + [z1]
@@ -45,45 +45,16 @@ def column_depth_table(grid, dtype=None):
     return (f[Nz] - f).to(dtype or g.dtype).to(torch.float64)
 
 
-def _depth_of_count(grid, dtype, device):
-    """the device copy of column_depth_table, built once per (grid, type) and kept with the grid"""
-    g = _bare(grid)
-    cache = g.__dict__.setdefault("_column_depth_table", {})
-    key = (dtype, str(device))
-    if key not in cache:
-        cache[key] = column_depth_table(g, dtype).to(dtype).to(device)
-    return cache[key]
-
-
-def _loc_names(loc):
-    return ", ".join("Nothing" if L is None else L.__name__ for L in loc)
-
-
 def _check(fields, what):
-    """`fields`: {name: Field or None} of u, v and the 2-D fields of one call.  The messages are continuity._check's."""
-    first = next((fields[n] for n in ("u", "v") if fields.get(n) is not None), None)
-    for name in ("u", "v"):
-        f = fields.get(name)
-        if f is None:
-            continue
-        if not isinstance(f, Field) or f.loc != _LOCS[name]:
-            raise TypeError(f"{what}: {name} must be a Field at ({_loc_names(_LOCS[name])})")
-        if not isinstance(first, Field):
-            continue                                               # u is no Field: reported in its own turn above
-        if f.grid is not first.grid:
-            raise ValueError(f"{what}: u and v must live on one grid")
-        if f.z_window is not None:
-            raise NotImplementedError(f"{what}: z-windowed fields are not handled")
-        if f.data.dtype != first.data.dtype or f.data.device != first.data.device:
-            raise ValueError(f"{what}: u, v and the 2-D fields must share one element type and device")
+    """`fields`: {name: Field or None} of u, v and the 2-D fields of one call: u and v through the shared checker (each may be None), then
+    what only the 2-D planes need -- they may live on another grid, which shares Nx, Ny and Hx with u's, and have one north/south halo."""
+    first = _check_fields({n: (fields[n], _LOCS[n]) for n in ("u", "v")}, what, "u and v", optional=("u", "v"),
+                          type_group="u, v and the 2-D fields")
     if first is None:
         raise TypeError(f"{what}: at least one of u at (Face, Center, Center) and v at (Center, Face, Center) is needed")
-    if not is_tripolar(first.grid):
-        raise TypeError(f"{what}: the fields' grid must be a TripolarGrid")
     planes = [(n, fields[n]) for n in ("U", "V", "Ubar", "Vbar") if fields.get(n) is not None]
     for name, f in planes:
-        if not isinstance(f, Field) or f.loc != _LOCS[name]:
-            raise TypeError(f"{what}: {name} must be a Field at ({_loc_names(_LOCS[name])})")
+        _require(f, name, _LOCS[name], what)
         if not is_tripolar(f.grid):
             raise TypeError(f"{what}: the fields' grid must be a TripolarGrid")
         if (f.Nx, f.Ny, f.Hx) != (first.Nx, first.Ny, first.Hx):
@@ -96,11 +67,7 @@ def _check(fields, what):
     return first
 
 
-def _ptr(f):
-    return None if f is None else f.data.data_ptr()
-
-
-class BarotropicModePlan:
+class BarotropicModePlan(OperatorPlan):
     """compute_barotropic_mode(u, v, U, V) with the arguments built once: `plan()` issues ONE tpg_barotropic_mode call on torch's current
     stream and then, with `fill_halos`, ONE HaloFillPlan of (U, V) -- their own conditions, the sign-flipping zipper into every north halo
     row they have.  It allocates nothing when called and is a single chain of launches, so it replays inside torch.cuda.graph.  A pair
@@ -119,22 +86,12 @@ class BarotropicModePlan:
         dtype, device = first.data.dtype, first.data.device
         lib = _lib.barotropic_lib()
         with torch.cuda.device(device):
-            dz = _dz_c(g, dtype, device)
-        self._held = [f.data for f in (u, v, U, V) if f is not None] + [dz]
+            dz = _grid_table(g, "_z_center_spacings", z_center_spacings, dtype, device)
+        held = [f.data for f in (u, v, U, V) if f is not None] + [dz]
         Hy2 = (U if U is not None else V).Hy
         args = (_ptr(u), _ptr(v), _ptr(U), _ptr(V), dz.data_ptr(), first.Nx, first.Ny, first.Nz, first.Hx, first.Hy, first.Hz, Hy2,
                 _lib.ft_of(dtype))
-        self._device, self._call = device, (lib.tpg_barotropic_mode, args)
-        outs = [f for f in (U, V) if f is not None and f.boundary_conditions is not None]
-        self._fill = HaloFillPlan(outs) if fill_halos and outs else None
-
-    def __call__(self):
-        fn, args = self._call
-        with torch.cuda.device(self._device):
-            _lib.check_barotropic(fn(*args, _lib.current_stream_ptr(self._device)))
-        if self._fill is not None:
-            self._fill()
-        return self
+        self._set_call(lib.tpg_barotropic_mode, args, _lib.check_barotropic, device, held, (U, V) if fill_halos else ())
 
 
 def barotropic_mode_plan(u, v, U=None, V=None, *, fill_halos=True):
@@ -152,7 +109,7 @@ def compute_barotropic_mode(u, v, U=None, V=None, *, fill_halos=True):
     return plan.U, plan.V
 
 
-class BarotropicCorrectionPlan:
+class BarotropicCorrectionPlan(OperatorPlan):
     """barotropic_correction(u, v, U, V, Ubar, Vbar) with the arguments built once: `plan()` issues, with Ubar / Vbar None, ONE
     tpg_barotropic_mode call into the plan's own planes, then ONE tpg_barotropic_correction call on torch's current stream and, with
     `fill_halos`, ONE HaloFillPlan of (u, v).  It allocates nothing when called and is a single chain of launches, so it replays inside
@@ -163,15 +120,15 @@ class BarotropicCorrectionPlan:
     def __init__(self, u, v, U, V, Ubar=None, Vbar=None, *, fill_halos=True, mask_immersed=True, what="barotropic_correction_plan"):
         for name, f in (("u", u), ("v", v), ("U", U), ("V", V)):
             if f is None:
-                raise TypeError(f"{what}: {name} must be a Field at ({_loc_names(_LOCS[name])})")
+                _require(f, name, _LOCS[name], what)
         if (Ubar is None) != (Vbar is None):
             raise TypeError(f"{what}: Ubar and Vbar are given together, or both left to the plan")
         _check({"u": u, "v": v, "U": U, "V": V, "Ubar": Ubar, "Vbar": Vbar}, what)
         self.u, self.v, self.U, self.V = u, v, U, V
-        self._mode = None
+        mode = ()
         if Ubar is None:                                           # the plan's own planes, beside U and V, filled by its own mode call
             Ubar, Vbar = Field(_LOCS["Ubar"], U.grid, name="Ubar"), Field(_LOCS["Vbar"], V.grid, name="Vbar")
-            self._mode = BarotropicModePlan(u, v, Ubar, Vbar, fill_halos=False, what=what)
+            mode = [BarotropicModePlan(u, v, Ubar, Vbar, fill_halos=False, what=what)]
         self.Ubar, self.Vbar = Ubar, Vbar
         g = _bare(u.grid)
         dtype, device = u.data.dtype, u.data.device
@@ -179,24 +136,10 @@ class BarotropicCorrectionPlan:
         counts = getattr(u.grid, "column_counts", None) if mask_immersed else None
         nfc, ncf = (None, None) if counts is None else (counts["fc"], counts["cf"])
         with torch.cuda.device(device):
-            depth = _depth_of_count(g, dtype, device)
-        self._held = [f.data for f in (u, v, U, V, Ubar, Vbar)] + [depth, nfc, ncf]
-        tptr = lambda t: None if t is None else t.data_ptr()
-        args = (_ptr(u), _ptr(v), _ptr(U), _ptr(V), _ptr(Ubar), _ptr(Vbar), depth.data_ptr(), tptr(nfc), tptr(ncf), 0.0,
-                u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, U.Hy, _lib.ft_of(dtype))
-        self._device, self._call = device, (lib.tpg_barotropic_correction, args)
-        outs = [f for f in (u, v) if f.boundary_conditions is not None]
-        self._fill = HaloFillPlan(outs) if fill_halos and outs else None
-
-    def __call__(self):
-        if self._mode is not None:
-            self._mode()
-        fn, args = self._call
-        with torch.cuda.device(self._device):
-            _lib.check_barotropic(fn(*args, _lib.current_stream_ptr(self._device)))
-        if self._fill is not None:
-            self._fill()
-        return self
+            depth = _grid_table(g, "_column_depth_table", column_depth_table, dtype, device)
+        held = [f.data for f in (u, v, U, V, Ubar, Vbar)] + [depth, nfc, ncf]
+        args = (*(_ptr(t) for t in held), 0.0, u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, U.Hy, _lib.ft_of(dtype))
+        self._set_call(lib.tpg_barotropic_correction, args, _lib.check_barotropic, device, held, (u, v) if fill_halos else (), before=mode)
 
 
 def barotropic_correction_plan(u, v, U, V, Ubar=None, Vbar=None, *, fill_halos=True, mask_immersed=True):

@@ -18,57 +18,20 @@ nothing (usable inside torch.cuda.graph)."""
 import torch
 
 from . import _lib
+from ._operator_plan import OperatorPlan, _check_fields, _ptr, _remembering_field
 from .boundary_conditions import Center, Face
-from .fields import Field, HaloFillPlan
-from .grids import is_tripolar
-from .reductions import _bare, _metric
+from .fields import Field
+from .reductions import _bare, _grid_table, _metric, z_center_spacings
 
 _LOCS = {"u": (Face, Center, Center), "v": (Center, Face, Center), "w": (Center, Center, Face), "div": (Center, Center, Center)}
 
 
-def z_center_spacings(grid, dtype=None):
-    """Δzᵃᵃᶜ[k] for k = 1..Nz: the face-to-face spacing at centre k, computed in float64 from grid.z_spec and rounded ONCE to `dtype` (default:
-    the grid's), as z_face_spacings is.  A regular interval (z0, z1) gives (z1 - z0) / Nz at every level; explicit faces give the float64
-    differences of adjacent faces.  A float64 host tensor of values that are exact in `dtype`."""
-    g = _bare(grid)
-    Nz = g.Nz
-    zz = g.z_spec.flatten().tolist() if torch.is_tensor(g.z_spec) else list(g.z_spec)
-    if len(zz) == 2:
-        d = torch.full((Nz,), (float(zz[1]) - float(zz[0])) / Nz, dtype=torch.float64)
-    else:
-        f = torch.tensor([float(z) for z in zz], dtype=torch.float64)
-        d = f[1:Nz + 1] - f[0:Nz]
-    return d.to(dtype or g.dtype).to(torch.float64)
-
-
-def _dz_c(grid, dtype, device):
-    """the device copy of z_center_spacings, built once per (grid, type) and kept with the grid"""
-    g = _bare(grid)
-    cache = g.__dict__.setdefault("_z_center_spacings", {})
-    key = (dtype, str(device))
-    if key not in cache:
-        cache[key] = z_center_spacings(g, dtype).to(dtype).to(device)
-    return cache[key]
-
-
 def _check(u, v, w, div, what="continuity"):
-    for name, f in (("u", u), ("v", v), ("w", w), ("div", div)):
-        if f is None and name in ("w", "div"):
-            continue
-        loc = _LOCS[name]
-        if not isinstance(f, Field) or f.loc != loc:
-            raise TypeError(f"{what}: {name} must be a Field at ({', '.join(L.__name__ for L in loc)})")
-        if f.grid is not u.grid:
-            raise ValueError(f"{what}: u, v, w and div must live on one grid")
-        if f.z_window is not None:
-            raise NotImplementedError(f"{what}: z-windowed fields are not handled")
-        if f.data.dtype != u.data.dtype or f.data.device != u.data.device:
-            raise ValueError(f"{what}: u, v, w and div must share one element type and device")
-    if not is_tripolar(u.grid):
-        raise TypeError(f"{what}: the fields' grid must be a TripolarGrid")
+    _check_fields({"u": (u, _LOCS["u"]), "v": (v, _LOCS["v"]), "w": (w, _LOCS["w"]), "div": (div, _LOCS["div"])}, what, "u, v, w and div",
+                  optional=("w", "div"))
 
 
-class ContinuityPlan:
+class ContinuityPlan(OperatorPlan):
     """compute_w_from_continuity(u, v, w) / horizontal_divergence(u, v, out=div) with the arguments built once: `plan()` issues ONE
     tpg_w_from_continuity call on torch's current stream and then, with `fill_halos`, ONE HaloFillPlan of the outputs it has -- the outputs'
     own conditions, whatever they are.  An impenetrable (Open) TOP on w would overwrite the computed surface value w[Nz+1]: a free-surface
@@ -89,23 +52,10 @@ class ContinuityPlan:
         ncc = None if counts is None else counts["cc"]
         with torch.cuda.device(device):
             dy, dx, az = (_metric(g, name, dtype, device) for name in ("dy_fc", "dx_cf", "az_cc"))
-            dz = _dz_c(g, dtype, device)
-        wd, dd = (None if f is None else f.data for f in (w, div))
-        self._held = [u.data, v.data, wd, dd, dy, dx, az, dz, ncc]
-        ptr = lambda t: None if t is None else t.data_ptr()
-        args = (u.data.data_ptr(), v.data.data_ptr(), ptr(wd), ptr(dd), dy.data_ptr(), dx.data_ptr(), az.data_ptr(), dz.data_ptr(),
-                ptr(ncc), 0.0, u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
-        self._device, self._call = device, (lib.tpg_w_from_continuity, args)
-        outs = [f for f in (w, div) if f is not None and f.boundary_conditions is not None]
-        self._fill = HaloFillPlan(outs) if fill_halos and outs else None
-
-    def __call__(self):
-        fn, args = self._call
-        with torch.cuda.device(self._device):
-            _lib.check_continuity(fn(*args, _lib.current_stream_ptr(self._device)))
-        if self._fill is not None:
-            self._fill()
-        return self
+            dz = _grid_table(g, "_z_center_spacings", z_center_spacings, dtype, device)
+        held = [u.data, v.data, None if w is None else w.data, None if div is None else div.data, dy, dx, az, dz, ncc]
+        args = (*(_ptr(t) for t in held), 0.0, u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
+        self._set_call(lib.tpg_w_from_continuity, args, _lib.check_continuity, device, held, (w, div) if fill_halos else ())
 
 
 def continuity_plan(u, v, w=None, div=None, *, fill_halos=True, mask_immersed=True):
@@ -138,7 +88,5 @@ def HorizontalDivergenceField(u, v, *, fill_halos=True, mask_immersed=True):
     holds zeros): compute_(field) runs the plan.  The plan works on a second Field object over the same tensor, so that the returned field and
     its plan form no reference cycle (a cycle would keep a multi-GB tensor alive until the cycle collector runs)."""
     _check(u, v, None, None, "HorizontalDivergenceField")
-    div = Field(_LOCS["div"], u.grid, name="div")
-    twin = Field(_LOCS["div"], u.grid, data=div.data, boundary_conditions=div.boundary_conditions, name="div")
-    div.operand_plan = ContinuityPlan(u, v, None, twin, fill_halos=fill_halos, mask_immersed=mask_immersed)
-    return div
+    return _remembering_field(_LOCS["div"], u.grid, "div",
+                              lambda twin: ContinuityPlan(u, v, None, twin, fill_halos=fill_halos, mask_immersed=mask_immersed))

@@ -35,7 +35,7 @@
 //
 // Fused mask (a count plane given): u nodes k <= n_fc (v: n_cf) get `mask_value` (converted once to T) instead -- bit for bit what
 // tpg_mask_immersed_fields leaves on u (plane fc, TPG_CENTER) and v (plane cf) after the unmasked call.
-#include "tpg_launch.hpp"
+#include "tpg_operator.hpp"
 #include "../../include/tripolar_hip_barotropic.h"
 
 // compile-time switches of the A/B in profiles/barotropic/ (make BAROTROPIC_TAG=_la8 BAROTROPIC_FLAGS='-DTPG_BARO_LOOKAHEAD=8', -DTPG_BARO_SEG=16,
@@ -58,15 +58,10 @@
 
 namespace {
 
-#if TPG_BARO_NT
-#define TPG_BARO_STORE(p, v) __builtin_nontemporal_store(v, p)
-#else
-#define TPG_BARO_STORE(p, v) (*(p) = (v))
-#endif
-
 constexpr int LA = TPG_BARO_LOOKAHEAD;     // the mode: levels whose loads are in flight ahead of the add
 constexpr int SEG = TPG_BARO_SEG;          // the correction: levels per work item
 constexpr int BATCH = TPG_BARO_BATCH;      // the correction: levels loaded before the first of them is stored
+constexpr bool NT = TPG_BARO_NT;          // the correction: u and v go out in ordinary stores
 
 struct ModePtrs {
     const void* src[2];                    // u and / or v, packed to the front
@@ -93,14 +88,10 @@ struct BaroArgs {
     double value;                          // the mask value (a T value held in a double)
 };
 
-template <int W> struct CellCounts { typedef int type __attribute__((ext_vector_type(W), aligned(4))); };
-
 template <typename T, int W, bool GEN>
 __global__ __launch_bounds__(256) void k_barotropic_mode(ModePtrs p, BaroArgs a)
 {
-    typedef typename Vec<T, W>::aligned_t vec_t;
-    typedef typename Vec<T, W>::loose_t lvec_t;
-    typedef typename std::conditional<GEN, lvec_t, vec_t>::type cvec_t;
+    typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= a.items) return;
     const int j = item / a.cpr;                                    // interior row (0-based)
@@ -137,9 +128,7 @@ __global__ __launch_bounds__(256) void k_barotropic_mode(ModePtrs p, BaroArgs a)
 template <typename T, int W, bool GEN, bool MASK>
 __global__ __launch_bounds__(256) void k_barotropic_correction(CorrPtrs p, BaroArgs a)
 {
-    typedef typename Vec<T, W>::aligned_t vec_t;
-    typedef typename Vec<T, W>::loose_t lvec_t;
-    typedef typename std::conditional<GEN, lvec_t, vec_t>::type cvec_t;
+    typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= a.items) return;
     const int seg = item / a.rowitems;
@@ -159,7 +148,7 @@ __global__ __launch_bounds__(256) void k_barotropic_correction(CorrPtrs p, BaroA
 #pragma unroll
     for (int e = 0; e < W; ++e) m[e] = 0;
     if (MASK && counts) {
-        const typename CellCounts<W>::type n = *reinterpret_cast<const typename CellCounts<W>::type*>(counts + (long long)a.Nx * j + e0);
+        const Counts<W> n = *reinterpret_cast<const Counts<W>*>(counts + (long long)a.Nx * j + e0);
 #pragma unroll
         for (int e = 0; e < W; ++e) m[e] = min(max(n[e], 0), a.Nz);  // masked levels (0-based k < m); the index into depth_of_count
     }
@@ -179,16 +168,9 @@ __global__ __launch_bounds__(256) void k_barotropic_correction(CorrPtrs p, BaroA
             cvec_t out;
 #pragma unroll
             for (int e = 0; e < W; ++e) out[e] = (MASK && k < m[e]) ? mv : x[b][e] + c[e];
-            TPG_BARO_STORE(reinterpret_cast<cvec_t*>(f + a.plane * k), out);
+            store_chunk<NT>(reinterpret_cast<cvec_t*>(f + a.plane * k), out);
         }
     }
-}
-
-// the arrays [p, p + pbytes) and [q, q + qbytes) share a byte
-bool arrays_overlap(const void* p, unsigned long long pbytes, const void* q, unsigned long long qbytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b ? b - a < pbytes : a - b < qbytes;
 }
 
 // the checks both calls start with, in this order
@@ -214,12 +196,12 @@ int tpg_barotropic_mode(const void* u, const void* v, void* Ubar, void* Vbar, co
     if (!u != !Ubar) { tpg::set_error("u and Ubar must be given together"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!v != !Vbar) { tpg::set_error("v and Vbar must be given together"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!dz_c) { tpg::set_error("null dz_c"); return TPG_ERR_INVALID_ARGUMENT; }
-    const size_t esz = ft == TPG_F64 ? 8 : 4;
-    if (((uintptr_t)u | (uintptr_t)v | (uintptr_t)Ubar | (uintptr_t)Vbar) % esz) {
+    const size_t esz = elem_size(ft);
+    if (misaligned(esz, u, v, Ubar, Vbar)) {
         tpg::set_error("u, v, Ubar or Vbar pointer not aligned to its element type");
         return TPG_ERR_INVALID_ARGUMENT;
     }
-    if ((uintptr_t)dz_c % esz) { tpg::set_error("dz_c pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
+    if (misaligned(esz, dz_c)) { tpg::set_error("dz_c pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
     const Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     const unsigned long long bytes = (unsigned long long)g.plane * (Nz + 2 * Hz) * esz;                    // u, v
     const unsigned long long pbytes = (unsigned long long)g.sx * (Ny + 2ll * Hy2) * esz;                   // Ubar, Vbar
@@ -243,7 +225,7 @@ int tpg_barotropic_mode(const void* u, const void* v, void* Ubar, void* Vbar, co
         typedef decltype(ty) T;
         const ChunkPlan cp = chunk_plan<T>(g, arrays, na);
         const int cpr = Nx / cp.W;
-        const BaroArgs a{ Nx, Ny, Nz, g.sx, cpr, Ny * cpr, Ny * cpr, g.plane, g.plane * Hz + (long long)g.sx * Hy + Hx, (long long)g.sx * Hy2 + Hx, 0.0 };
+        const BaroArgs a{ Nx, Ny, Nz, g.sx, cpr, Ny * cpr, Ny * cpr, g.plane, interior3(g), (long long)g.sx * Hy2 + Hx, 0.0 };
         dim3 grid((unsigned)((a.items + 255) / 256), (unsigned)nf);
         dispatch_chunk<T>(cp.W, cp.gen, [&](auto cw, auto gen) {
             hipLaunchKernelGGL((k_barotropic_mode<T, decltype(cw)::value, decltype(gen)::value>), grid, dim3(256), 0, st, p, a);
@@ -261,13 +243,13 @@ int tpg_barotropic_correction(void* u, void* v, const void* U, const void* V, co
     if (!u != !U || !u != !Ubar) { tpg::set_error("u, U and Ubar must be given together"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!v != !V || !v != !Vbar) { tpg::set_error("v, V and Vbar must be given together"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!depth_of_count) { tpg::set_error("null depth_of_count"); return TPG_ERR_INVALID_ARGUMENT; }
-    const size_t esz = ft == TPG_F64 ? 8 : 4;
-    if (((uintptr_t)u | (uintptr_t)v | (uintptr_t)U | (uintptr_t)V | (uintptr_t)Ubar | (uintptr_t)Vbar) % esz) {
+    const size_t esz = elem_size(ft);
+    if (misaligned(esz, u, v, U, V, Ubar, Vbar)) {
         tpg::set_error("u, v, U, V, Ubar or Vbar pointer not aligned to its element type");
         return TPG_ERR_INVALID_ARGUMENT;
     }
-    if ((uintptr_t)depth_of_count % esz) { tpg::set_error("depth_of_count pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (((uintptr_t)n_fc | (uintptr_t)n_cf) % 4) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }
+    if (misaligned(esz, depth_of_count)) { tpg::set_error("depth_of_count pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
+    if (misaligned(4, n_fc, n_cf)) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }
     const Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     const unsigned long long bytes = (unsigned long long)g.plane * (Nz + 2 * Hz) * esz;                    // u, v
     const unsigned long long pbytes = (unsigned long long)g.sx * (Ny + 2ll * Hy2) * esz;                   // U, V, Ubar, Vbar
@@ -293,7 +275,7 @@ int tpg_barotropic_correction(void* u, void* v, const void* U, const void* V, co
         typedef decltype(ty) T;
         const ChunkPlan cp = chunk_plan<T>(g, arrays, na);
         const int cpr = Nx / cp.W;
-        const BaroArgs a{ Nx, Ny, Nz, g.sx, cpr, Ny * cpr, (int)(segs * Ny * cpr), g.plane, g.plane * Hz + (long long)g.sx * Hy + Hx,
+        const BaroArgs a{ Nx, Ny, Nz, g.sx, cpr, Ny * cpr, (int)(segs * Ny * cpr), g.plane, interior3(g),
                           (long long)g.sx * Hy2 + Hx, mask ? (double)(T)mask_value : 0.0 };
         dim3 grid((unsigned)((a.items + 255) / 256), (unsigned)nf);
         dispatch_chunk<T>(cp.W, cp.gen, [&](auto cw, auto gen) {

@@ -45,7 +45,7 @@
 // Fused mask (n_cc given): the scan runs on the unmasked values (levels under the mask ARE read: a model's u and v are masked there); where
 // they are stored, div nodes k <= n and w faces k <= min(n + 1, Nz) get `mask_value` (converted once to T) instead -- bit for bit what
 // tpg_mask_immersed_fields leaves on w (TPG_FACE) and div (TPG_CENTER) with that plane.
-#include "tpg_launch.hpp"
+#include "tpg_operator.hpp"
 #include "../../include/tripolar_hip_continuity.h"
 
 // compile-time switches of the A/B in profiles/continuity/ (make CONTINUITY_FLAGS='-DTPG_CONT_JT=4 -DTPG_CONT_LOOKAHEAD=1' or -DTPG_CONT_NT=0)
@@ -61,14 +61,9 @@
 
 namespace {
 
-#if TPG_CONT_NT
-#define TPG_CONT_STORE(p, v) __builtin_nontemporal_store(v, p)
-#else
-#define TPG_CONT_STORE(p, v) (*(p) = (v))
-#endif
-
 constexpr int JT = TPG_CONT_JT;            // rows per work item
 constexpr int LA = TPG_CONT_LOOKAHEAD;     // levels whose loads are in flight ahead of the arithmetic
+constexpr bool NT = TPG_CONT_NT;          // w and div go out in streaming stores
 
 struct ContPtrs {
     const void *u, *v;
@@ -87,14 +82,10 @@ struct ContArgs {
     double value;                          // the mask value (a T value held in a double)
 };
 
-template <int W> struct CellCounts { typedef int type __attribute__((ext_vector_type(W), aligned(4))); };
-
 template <typename T, int W, bool GEN, bool MASK, bool HAS_W, bool HAS_DIV>
 __global__ __launch_bounds__(256) void k_w_from_continuity(ContPtrs p, ContArgs a)
 {
-    typedef typename Vec<T, W>::aligned_t vec_t;
-    typedef typename Vec<T, W>::loose_t lvec_t;
-    typedef typename std::conditional<GEN, lvec_t, vec_t>::type cvec_t;
+    typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= a.items) return;
     const int tile = item / a.cpr;
@@ -125,8 +116,7 @@ __global__ __launch_bounds__(256) void k_w_from_continuity(ContPtrs p, ContArgs 
 #pragma unroll
         for (int e = 0; e < W; ++e) { dyc[r][e] = y[e]; azr[r][e] = z[e]; wr[r][e] = T(0); m[r][e] = 0; }
         if constexpr (MASK) {
-            const typename CellCounts<W>::type n =
-                *reinterpret_cast<const typename CellCounts<W>::type*>(p.ncc + (long long)a.Nx * (j0 + min(r, nr - 1)) + e0);
+            const Counts<W> n = *reinterpret_cast<const Counts<W>*>(p.ncc + (long long)a.Nx * (j0 + min(r, nr - 1)) + e0);
 #pragma unroll
             for (int e = 0; e < W; ++e) m[r][e] = min(n[e], a.Nz);  // masked div levels (0-based k < m); w faces f < min(m + 1, Nz)
         }
@@ -169,7 +159,7 @@ __global__ __launch_bounds__(256) void k_w_from_continuity(ContPtrs p, ContArgs 
             cvec_t out;
 #pragma unroll
             for (int e = 0; e < W; ++e) out[e] = (MASK && 0 < min(m[r][e] + 1, a.Nz)) ? mv : T(0);
-            if (r < nr) TPG_CONT_STORE(reinterpret_cast<cvec_t*>(w + a.sx * r), out);
+            if (r < nr) store_chunk<NT>(reinterpret_cast<cvec_t*>(w + a.sx * r), out);
         }
     }
 
@@ -211,19 +201,12 @@ __global__ __launch_bounds__(256) void k_w_from_continuity(ContPtrs p, ContArgs 
                 }
                 if (r < nr) {
                     const long long o = a.plane * k + a.sx * r;
-                    if constexpr (HAS_DIV) TPG_CONT_STORE(reinterpret_cast<cvec_t*>(div + o), dout);
-                    if constexpr (HAS_W) TPG_CONT_STORE(reinterpret_cast<cvec_t*>(w + o + a.plane), wout);
+                    if constexpr (HAS_DIV) store_chunk<NT>(reinterpret_cast<cvec_t*>(div + o), dout);
+                    if constexpr (HAS_W) store_chunk<NT>(reinterpret_cast<cvec_t*>(w + o + a.plane), wout);
                 }
             }
         }
     }
-}
-
-// the parents [p, p + pbytes) and [q, q + qbytes) share a byte
-bool parents_overlap(const void* p, unsigned long long pbytes, const void* q, unsigned long long qbytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b ? b - a < pbytes : a - b < qbytes;
 }
 
 }  // namespace
@@ -241,12 +224,12 @@ int tpg_w_from_continuity(const void* u, const void* v, void* w, void* div, cons
     if (!u || !v) { tpg::set_error("null u or v"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!w && !div) { tpg::set_error("w and div both null: nothing to compute"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!dy_fc || !dx_cf || !az_cc || !dz_c) { tpg::set_error("null dy_fc, dx_cf, az_cc or dz_c"); return TPG_ERR_INVALID_ARGUMENT; }
-    const size_t esz = ft == TPG_F64 ? 8 : 4;
-    if (((uintptr_t)u | (uintptr_t)v | (uintptr_t)w | (uintptr_t)div) % esz) {
+    const size_t esz = elem_size(ft);
+    if (misaligned(esz, u, v, w, div)) {
         tpg::set_error("u, v, w or div pointer not aligned to its element type");
         return TPG_ERR_INVALID_ARGUMENT;
     }
-    if (((uintptr_t)dy_fc | (uintptr_t)dx_cf | (uintptr_t)az_cc | (uintptr_t)dz_c) % esz) {
+    if (misaligned(esz, dy_fc, dx_cf, az_cc, dz_c)) {
         tpg::set_error("dy_fc, dx_cf, az_cc or dz_c pointer not aligned to its element type");
         return TPG_ERR_INVALID_ARGUMENT;
     }
@@ -254,15 +237,15 @@ int tpg_w_from_continuity(const void* u, const void* v, void* w, void* div, cons
     const Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     const unsigned long long bytes = (unsigned long long)g.plane * (Nz + 2 * Hz) * esz;            // u, v, div
     const unsigned long long wbytes = (unsigned long long)g.plane * (Nz + 1 + 2 * Hz) * esz;       // w: one more level
-    if (w && (parents_overlap(w, wbytes, u, bytes) || parents_overlap(w, wbytes, v, bytes))) {
+    if (w && (arrays_overlap(w, wbytes, u, bytes) || arrays_overlap(w, wbytes, v, bytes))) {
         tpg::set_error("w's parent overlaps u's or v's (every column reads cells while its neighbours' columns write)");
         return TPG_ERR_INVALID_ARGUMENT;
     }
-    if (div && (parents_overlap(div, bytes, u, bytes) || parents_overlap(div, bytes, v, bytes))) {
+    if (div && (arrays_overlap(div, bytes, u, bytes) || arrays_overlap(div, bytes, v, bytes))) {
         tpg::set_error("div's parent overlaps u's or v's (every column reads cells while its neighbours' columns write)");
         return TPG_ERR_INVALID_ARGUMENT;
     }
-    if (w && div && parents_overlap(w, wbytes, div, bytes)) { tpg::set_error("w's parent overlaps div's"); return TPG_ERR_INVALID_ARGUMENT; }
+    if (w && div && arrays_overlap(w, wbytes, div, bytes)) { tpg::set_error("w's parent overlaps div's"); return TPG_ERR_INVALID_ARGUMENT; }
     if (Hx < 1 || Hy < 1) {
         tpg::set_error("the rule reads u[i+1, j] and v[i, j+1]: Hx >= 1 and Hy >= 1 needed (halo (%d,%d))", Hx, Hy);
         return TPG_ERR_UNSUPPORTED;
@@ -279,8 +262,7 @@ int tpg_w_from_continuity(const void* u, const void* v, void* w, void* div, cons
         typedef decltype(ty) T;
         const ChunkPlan cp = chunk_plan<T>(g, arrays, na);
         const int cpr = Nx / cp.W;
-        const long long off2 = (long long)g.sx * Hy + Hx;
-        const ContArgs a{ Nx, Ny, Nz, g.sx, cpr, (int)(tiles * cpr), g.plane, off2, g.plane * Hz + off2, n_cc ? (double)(T)mask_value : 0.0 };
+        const ContArgs a{ Nx, Ny, Nz, g.sx, cpr, (int)(tiles * cpr), g.plane, interior2(g), interior3(g), n_cc ? (double)(T)mask_value : 0.0 };
         dim3 grid((unsigned)((a.items + 255) / 256));
         dispatch_chunk<T>(cp.W, cp.gen, [&](auto cw, auto gen) {
             constexpr int W = decltype(cw)::value;

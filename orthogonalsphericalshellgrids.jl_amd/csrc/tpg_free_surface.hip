@@ -27,7 +27,7 @@
 // eta, U, V ping-pong: an item reads only the `_in` arrays and writes only the `_out` ones, so no item reads a cell another writes.
 // 16-B chunks where rows and pointers sit on the 16-B grid, the same chunks element-aligned otherwise: chunk_plan's plain / GEN split over
 // all the planes passed.  Element offsets are 64-bit.  No atomics, no LDS, nothing allocated, no host wait.
-#include "tpg_launch.hpp"
+#include "tpg_operator.hpp"
 #include "../../include/tripolar_hip_free_surface.h"
 
 // compile-time switch of the A/B in profiles/free_surface/ (make FREE_SURFACE_TAG=_jt4 FREE_SURFACE_FLAGS=-DTPG_FS_JT=4).  Measured at
@@ -57,14 +57,10 @@ struct FsArgs {
     double dtau, g, weight;                // T values held in doubles
 };
 
-template <int W> struct CellCounts { typedef int type __attribute__((ext_vector_type(W), aligned(4))); };
-
 template <typename T, int W, bool GEN, bool COUNTS, bool AVG>
 __global__ __launch_bounds__(256) void k_free_surface_substep(FsPtrs p, FsArgs a)
 {
-    typedef typename Vec<T, W>::aligned_t vec_t;
-    typedef typename Vec<T, W>::loose_t lvec_t;
-    typedef typename std::conditional<GEN, lvec_t, vec_t>::type cvec_t;
+    typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= a.items) return;
     const int tile = item / a.cpr;
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(256) void k_free_surface_substep(FsPtrs p, FsArgs a
 #pragma unroll
         for (int e = 0; e < W; ++e) gHu[e] = gHv[e] = g * depth[0];
         if constexpr (COUNTS) {
-            typedef typename CellCounts<W>::type counts_t;
+            typedef Counts<W> counts_t;
             if (p.nfc) {
                 const counts_t n = *reinterpret_cast<const counts_t*>(p.nfc + (long long)a.Nx * j + e0);
 #pragma unroll
@@ -189,13 +185,6 @@ __global__ __launch_bounds__(256) void k_free_surface_substep(FsPtrs p, FsArgs a
     }
 }
 
-// the arrays [p, p + pbytes) and [q, q + qbytes) share a byte
-bool arrays_overlap(const void* p, unsigned long long pbytes, const void* q, unsigned long long qbytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b ? b - a < pbytes : a - b < qbytes;
-}
-
 }  // namespace
 
 extern "C" {
@@ -220,16 +209,16 @@ int tpg_free_surface_substep(void* eta_out, void* U_out, void* V_out, const void
     if (!dy_fc || !dx_cf || !az_cc || !dx_fc || !dy_cf) { tpg::set_error("null dy_fc, dx_cf, az_cc, dx_fc or dy_cf"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!depth_of_count) { tpg::set_error("null depth_of_count"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!eta_bar != !U_bar || !eta_bar != !V_bar) { tpg::set_error("eta_bar, U_bar and V_bar must be given together"); return TPG_ERR_INVALID_ARGUMENT; }
-    const size_t esz = ft == TPG_F64 ? 8 : 4;
+    const size_t esz = elem_size(ft);
     const int NP = 16;
     const void* const planes[NP] = { eta_out, U_out, V_out, eta_bar, U_bar, V_bar, eta_in, U_in, V_in, GU, GV, dy_fc, dx_cf, az_cc, dx_fc, dy_cf };
     const char* const names[NP] = { "eta_out", "U_out", "V_out", "eta_bar", "U_bar", "V_bar", "eta_in", "U_in", "V_in", "GU", "GV",
                                     "dy_fc", "dx_cf", "az_cc", "dx_fc", "dy_cf" };
     const int NW = 6;                                              // the first NW are written
     for (int q = 0; q < NP; ++q)
-        if ((uintptr_t)planes[q] % esz) { tpg::set_error("%s pointer not aligned to its element type", names[q]); return TPG_ERR_INVALID_ARGUMENT; }
-    if ((uintptr_t)depth_of_count % esz) { tpg::set_error("depth_of_count pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (((uintptr_t)n_fc | (uintptr_t)n_cf) % 4) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }
+        if (misaligned(esz, planes[q])) { tpg::set_error("%s pointer not aligned to its element type", names[q]); return TPG_ERR_INVALID_ARGUMENT; }
+    if (misaligned(esz, depth_of_count)) { tpg::set_error("depth_of_count pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
+    if (misaligned(4, n_fc, n_cf)) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }
     if ((long long)(Nx + 2ll * Hx) * (Ny + 2ll * Hy2) >= (1ll << 31)) { tpg::set_error("free surface: plane too large for 32-bit row offsets"); return TPG_ERR_UNSUPPORTED; }
     const Geom gm = tpg::make_geom(Nx, Ny, 1, Hx, Hy2, 0);
     const unsigned long long pbytes = (unsigned long long)gm.plane * esz;
@@ -259,7 +248,7 @@ int tpg_free_surface_substep(void* eta_out, void* U_out, void* V_out, const void
         typedef decltype(ty) T;
         const ChunkPlan cp = chunk_plan<T>(gm, arrays, na);
         const int cpr = Nx / cp.W;
-        const FsArgs a{ Nx, Ny, Nz, gm.sx, cpr, (int)(tiles * cpr), (long long)gm.sx * Hy2 + Hx, (double)(T)dtau, (double)(T)g, (double)(T)weight };
+        const FsArgs a{ Nx, Ny, Nz, gm.sx, cpr, (int)(tiles * cpr), interior2(gm), (double)(T)dtau, (double)(T)g, (double)(T)weight };
         dim3 grid((unsigned)((a.items + 255) / 256));
         dispatch_chunk<T>(cp.W, cp.gen, [&](auto cw, auto gen) {
             constexpr int W = decltype(cw)::value;

@@ -31,7 +31,7 @@
 // (Face, Face, Center) field -- and nothing is computed there: a chunk row whose elements are all masked at a level is a single vector store
 // and loads nothing; a row with some masked elements is computed whole and the masked elements replaced, so nothing a masked node would have
 // read (a NaN under land) reaches the output.
-#include "tpg_launch.hpp"
+#include "tpg_operator.hpp"
 #include "../../include/tripolar_hip_operators.h"
 
 // compile-time switches of the A/B in profiles/vorticity/ (make OPERATORS_FLAGS='-DTPG_VORT_JT=8' or -DTPG_VORT_NT=0).  Measured at
@@ -47,13 +47,8 @@
 
 namespace {
 
-#if TPG_VORT_NT
-#define TPG_VORT_STORE(p, v) __builtin_nontemporal_store(v, p)
-#else
-#define TPG_VORT_STORE(p, v) (*(p) = (v))
-#endif
-
 constexpr int JT = TPG_VORT_JT;            // rows per work item
+constexpr bool NT = TPG_VORT_NT;          // zeta goes out in streaming stores
 constexpr int VORT_LEVELS = 16;            // levels per segment (the product's; TPG_VORTICITY_LEVELS in the test library)
 
 struct VortPtrs {
@@ -74,14 +69,10 @@ struct VortArgs {
     double value;                          // the mask value (a T value held in a double)
 };
 
-template <int W> struct NodeCounts { typedef int type __attribute__((ext_vector_type(W), aligned(4))); };
-
 template <typename T, int W, bool GEN, bool MASK>
 __global__ __launch_bounds__(256) void k_vertical_vorticity(VortPtrs p, VortArgs a)
 {
-    typedef typename Vec<T, W>::aligned_t vec_t;
-    typedef typename Vec<T, W>::loose_t lvec_t;
-    typedef typename std::conditional<GEN, lvec_t, vec_t>::type cvec_t;
+    typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
     if (item >= a.items) return;
     const int tile = item / a.cpr;
@@ -107,8 +98,7 @@ __global__ __launch_bounds__(256) void k_vertical_vorticity(VortPtrs p, VortArgs
         for (int e = 0; e < W; ++e) { dyc[r][e] = y[e]; azr[r][e] = z[e]; }
         lo[r] = 0;
         if constexpr (MASK) {
-            const typename NodeCounts<W>::type n =
-                *reinterpret_cast<const typename NodeCounts<W>::type*>(p.nff + (long long)a.Nx * (j0 + rr) + e0);
+            const Counts<W> n = *reinterpret_cast<const Counts<W>*>(p.nff + (long long)a.Nx * (j0 + rr) + e0);
             lo[r] = a.Nz;
 #pragma unroll
             for (int e = 0; e < W; ++e) {
@@ -138,7 +128,7 @@ __global__ __launch_bounds__(256) void k_vertical_vorticity(VortPtrs p, VortArgs
             if (r >= nr) break;
             const long long o = o3 + a.sx * r;
             if (MASK && k < lo[r]) {                               // every node of the chunk row is masked: nothing is read
-                TPG_VORT_STORE(reinterpret_cast<cvec_t*>(zeta + o), (cvec_t)(mv));
+                store_chunk<NT>(reinterpret_cast<cvec_t*>(zeta + o), (cvec_t)(mv));
                 have = false;
                 continue;
             }
@@ -161,16 +151,9 @@ __global__ __launch_bounds__(256) void k_vertical_vorticity(VortPtrs p, VortArgs
                 d[e] = c;
             }
             have = true;
-            TPG_VORT_STORE(reinterpret_cast<cvec_t*>(zeta + o), out);
+            store_chunk<NT>(reinterpret_cast<cvec_t*>(zeta + o), out);
         }
     }
-}
-
-// the parents [p, p + bytes) and [q, q + bytes) share a byte
-bool parents_overlap(const void* p, const void* q, unsigned long long bytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b ? b - a < bytes : a - b < bytes;
 }
 
 }  // namespace
@@ -186,16 +169,16 @@ int tpg_vertical_vorticity(const void* u, const void* v, void* zeta, const void*
     if (int rc = tpg::check_geom(Nx, Ny, Nz, Hx, Hy, Hz, ft)) return rc;
     if (!u || !v || !zeta) { tpg::set_error("null u, v or zeta"); return TPG_ERR_INVALID_ARGUMENT; }
     if (!dx_fc || !dy_cf || !az_ff) { tpg::set_error("null dx_fc, dy_cf or az_ff"); return TPG_ERR_INVALID_ARGUMENT; }
-    const size_t esz = ft == TPG_F64 ? 8 : 4;
-    if (((uintptr_t)u | (uintptr_t)v | (uintptr_t)zeta) % esz) { tpg::set_error("u, v or zeta pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (((uintptr_t)dx_fc | (uintptr_t)dy_cf | (uintptr_t)az_ff) % esz) {
+    const size_t esz = elem_size(ft);
+    if (misaligned(esz, u, v, zeta)) { tpg::set_error("u, v or zeta pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
+    if (misaligned(esz, dx_fc, dy_cf, az_ff)) {
         tpg::set_error("dx_fc, dy_cf or az_ff pointer not aligned to its element type");
         return TPG_ERR_INVALID_ARGUMENT;
     }
     if ((uintptr_t)n_ff % 4) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }
     const Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
     const unsigned long long bytes = (unsigned long long)g.plane * (Nz + 2 * Hz) * esz;
-    if (parents_overlap(zeta, u, bytes) || parents_overlap(zeta, v, bytes)) {
+    if (arrays_overlap(zeta, bytes, u, bytes) || arrays_overlap(zeta, bytes, v, bytes)) {
         tpg::set_error("zeta's parent overlaps u's or v's (every node reads cells its neighbours' nodes write)");
         return TPG_ERR_INVALID_ARGUMENT;
     }
@@ -214,9 +197,7 @@ int tpg_vertical_vorticity(const void* u, const void* v, void* zeta, const void*
         typedef decltype(ty) T;
         const ChunkPlan cp = chunk_plan<T>(g, arrays, 6);
         const int cpr = Nx / cp.W;
-        const long long off2 = (long long)g.sx * Hy + Hx;
-        const VortArgs a{ Nx, Ny, Nz, g.sx, cpr, (int)(tiles * cpr), levels, g.plane, off2, g.plane * Hz + off2,
-                          (double)(T)mask_value };
+        const VortArgs a{ Nx, Ny, Nz, g.sx, cpr, (int)(tiles * cpr), levels, g.plane, interior2(g), interior3(g), (double)(T)mask_value };
         dim3 grid((unsigned)((a.items + 255) / 256), (unsigned)((Nz + levels - 1) / levels));
         dispatch_chunk<T>(cp.W, cp.gen, [&](auto w, auto gen) {
             if (n_ff) hipLaunchKernelGGL((k_vertical_vorticity<T, decltype(w)::value, decltype(gen)::value, true>), grid, dim3(256), 0, st, p, a);

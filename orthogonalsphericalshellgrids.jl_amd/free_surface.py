@@ -19,11 +19,12 @@ Out of scope: AB3 sub-stepping, the free-surface mask, transport-weighted averag
 import torch
 
 from . import _lib
-from .barotropic import _depth_of_count, _loc_names
+from ._operator_plan import OperatorPlan, _check_fields, _ptr, _refuse_window
+from .barotropic import column_depth_table
 from .boundary_conditions import Center, Face
 from .fields import Field, HaloFillPlan
 from .grids import is_tripolar, with_halo
-from .reductions import _bare
+from .reductions import _bare, _grid_table
 
 g_Earth = 9.80665                                                  # Oceananigans' default gravitational_acceleration [recalled]
 
@@ -37,23 +38,15 @@ def _loc_of(name):
 
 def _check(fields, what):
     """`fields`: {name: Field} of one sub-step: eta_out, U_out, V_out, eta, U, V, GU, GV and, together or not at all, eta_bar, U_bar, V_bar.
-    The messages are barotropic._check's.  Returns the first field."""
-    first = None
-    for name, f in fields.items():
-        if isinstance(f, Field) and f.z_window is not None:
-            raise NotImplementedError(f"{what}: z-windowed fields are not handled")
-        if not isinstance(f, Field) or f.loc != _loc_of(name):
-            raise TypeError(f"{what}: {name} must be a Field at ({_loc_names(_loc_of(name))})")
-        if first is None:
-            first = f
-            if not is_tripolar(f.grid):
-                raise TypeError(f"{what}: the fields' grid must be a TripolarGrid")
-            if getattr(_bare(f.grid).architecture, "is_distributed", False):
-                raise NotImplementedError(f"{what}: distributed sub-cycling is not provided")
-        if f.grid is not first.grid:
-            raise ValueError(f"{what}: the fields of a sub-step must live on one grid (the free surface's extended-halo grid)")
-        if f.data.dtype != first.data.dtype or f.data.device != first.data.device:
-            raise ValueError(f"{what}: the fields of a sub-step must share one element type and device")
+    A z-windowed 3-D field is refused as z-windowed, before its location is looked at; the rest is the shared checker's, then the refusal
+    of a distributed grid.  Returns the first field."""
+    for f in fields.values():
+        if isinstance(f, Field):
+            _refuse_window(f, what)
+    first = _check_fields({name: (f, _loc_of(name)) for name, f in fields.items()}, what, "the fields of a sub-step",
+                          grid_note=" (the free surface's extended-halo grid)")
+    if getattr(_bare(first.grid).architecture, "is_distributed", False):
+        raise NotImplementedError(f"{what}: distributed sub-cycling is not provided")
     return first
 
 
@@ -71,7 +64,7 @@ def _column_grid(grid, first, what):
     return (None, None) if counts is None else (counts["fc"], counts["cf"])
 
 
-class _Substep:
+class _Substep(OperatorPlan):
     """one tpg_free_surface_substep call with the arguments built once; `weight` None: no averaging"""
 
     def __init__(self, out, state, G, averages, dtau, g, weight, grid, what):
@@ -86,18 +79,12 @@ class _Substep:
         if any(m.dtype != dtype or m.device != device for m in metrics):
             raise ValueError(f"{what}: the fields must have the element type and device of their grid's metrics")
         with torch.cuda.device(device):
-            depth = _depth_of_count(ext, dtype, device)
-        self._held = [f.data for f in names.values()] + metrics + [depth, nfc, ncf]
-        ptr = lambda t: None if t is None else t.data_ptr()
-        bars = [None] * 3 if averages is None else [f.data for f in averages]
-        self._args = (*(f.data.data_ptr() for f in (*out, *state, *G)), *(ptr(t) for t in bars), *(m.data_ptr() for m in metrics),
-                      depth.data_ptr(), ptr(nfc), ptr(ncf), float(dtau), float(g), 0.0 if weight is None else float(weight),
-                      first.Nx, first.Ny, ext.Nz, first.Hx, first.Hy, _lib.ft_of(dtype))
-        self._device, self._fn = device, _lib.free_surface_lib().tpg_free_surface_substep
-
-    def __call__(self):
-        with torch.cuda.device(self._device):
-            _lib.check_free_surface(self._fn(*self._args, _lib.current_stream_ptr(self._device)))
+            depth = _grid_table(ext, "_column_depth_table", column_depth_table, dtype, device)
+        held = [f.data for f in names.values()] + metrics + [depth, nfc, ncf]
+        bars = [None] * 3 if averages is None else averages
+        self._args = (*(_ptr(t) for t in (*out, *state, *G, *bars, *metrics, depth, nfc, ncf)), float(dtau), float(g),
+                      0.0 if weight is None else float(weight), first.Nx, first.Ny, ext.Nz, first.Hx, first.Hy, _lib.ft_of(dtype))
+        self._set_call(_lib.free_surface_lib().tpg_free_surface_substep, self._args, _lib.check_free_surface, device, held)
 
 
 def split_explicit_substep(eta_out, U_out, V_out, eta, U, V, GU, GV, dtau, *, gravitational_acceleration=g_Earth, averages=None, weight=1.0,

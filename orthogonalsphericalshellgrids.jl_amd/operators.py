@@ -12,31 +12,20 @@ allocates nothing (usable inside torch.cuda.graph)."""
 import torch
 
 from . import _lib
+from ._operator_plan import OperatorPlan, _check_fields, _ptr, _remembering_field
 from .boundary_conditions import Center, Face
-from .fields import Field, HaloFillPlan
-from .grids import is_tripolar
+from .fields import Field
 from .reductions import _bare, _metric
 
-_LOCS = (("u", (Face, Center, Center)), ("v", (Center, Face, Center)), ("zeta", (Face, Face, Center)))
+_LOCS = {"u": (Face, Center, Center), "v": (Center, Face, Center), "zeta": (Face, Face, Center)}
 
 
 def _check(u, v, zeta):
-    for f, (name, loc) in zip((u, v, zeta), _LOCS):
-        if f is None and name == "zeta":
-            continue
-        if not isinstance(f, Field) or f.loc != loc:
-            raise TypeError(f"vertical_vorticity: {name} must be a Field at ({', '.join(L.__name__ for L in loc)})")
-        if f.grid is not u.grid:
-            raise ValueError("vertical_vorticity: u, v and zeta must live on one grid")
-        if f.z_window is not None:
-            raise NotImplementedError("vertical_vorticity: z-windowed fields are not handled")
-        if f.data.dtype != u.data.dtype or f.data.device != u.data.device:
-            raise ValueError("vertical_vorticity: u, v and zeta must share one element type and device")
-    if not is_tripolar(u.grid):
-        raise TypeError("vertical_vorticity: the fields' grid must be a TripolarGrid")
+    _check_fields({"u": (u, _LOCS["u"]), "v": (v, _LOCS["v"]), "zeta": (zeta, _LOCS["zeta"])}, "vertical_vorticity", "u, v and zeta",
+                  optional=("zeta",))
 
 
-class VorticityPlan:
+class VorticityPlan(OperatorPlan):
     """vertical_vorticity(u, v, out=zeta) with its arguments built once: `plan()` issues one tpg_vertical_vorticity call and, with
     `fill_halos`, ζ's halo fill (a HaloFillPlan of zeta) on torch's current stream; it allocates nothing and is a single chain of launches,
     so it replays inside torch.cuda.graph (serial grids: a seam exchange cannot be captured).  On an ImmersedBoundaryGrid with
@@ -55,18 +44,12 @@ class VorticityPlan:
         nff = None if counts is None else counts["ff"]
         with torch.cuda.device(device):
             dx, dy, az = (_metric(g, name, dtype, device) for name in ("dx_fc", "dy_cf", "az_ff"))
-        self._held = [u.data, v.data, zeta.data, dx, dy, az, nff]
-        args = (u.data.data_ptr(), v.data.data_ptr(), zeta.data.data_ptr(), dx.data_ptr(), dy.data_ptr(), az.data_ptr(),
-                None if nff is None else nff.data_ptr(), 0.0, u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
-        self._device, self._call = device, (lib.tpg_vertical_vorticity, args)
-        self._fill = HaloFillPlan([zeta]) if fill_halos and zeta.boundary_conditions is not None else None
+        held = [u.data, v.data, zeta.data, dx, dy, az, nff]
+        args = (*(_ptr(t) for t in held), 0.0, u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
+        self._set_call(lib.tpg_vertical_vorticity, args, _lib.check_operators, device, held, [zeta] if fill_halos else ())
 
     def __call__(self):
-        fn, args = self._call
-        with torch.cuda.device(self._device):
-            _lib.check_operators(fn(*args, _lib.current_stream_ptr(self._device)))
-        if self._fill is not None:
-            self._fill()
+        super().__call__()
         return self.zeta
 
 
@@ -82,7 +65,7 @@ def vertical_vorticity(u, v, out=None, *, fill_halos=True, mask_immersed=True):
     ImmersedBoundaryGrid with `mask_immersed` the peripheral ζ nodes are 0, as mask_immersed_field(ζ) would leave them.  z-windowed and
     reduced fields are refused.  Builds a VorticityPlan and runs it once; use vorticity_plan for a field computed on every output."""
     _check(u, v, out)
-    zeta = Field((Face, Face, Center), u.grid, name="zeta") if out is None else out
+    zeta = Field(_LOCS["zeta"], u.grid, name="zeta") if out is None else out
     return VorticityPlan(u, v, zeta, fill_halos=fill_halos, mask_immersed=mask_immersed)()
 
 
@@ -92,10 +75,8 @@ def VerticalVorticityField(u, v, *, fill_halos=True, mask_immersed=True):
     object over the same tensor, so that the returned field and its plan form no reference cycle (a cycle would keep a multi-GB tensor
     alive until the cycle collector runs)."""
     _check(u, v, None)
-    zeta = Field((Face, Face, Center), u.grid, name="zeta")
-    twin = Field((Face, Face, Center), u.grid, data=zeta.data, boundary_conditions=zeta.boundary_conditions, name="zeta")
-    zeta.operand_plan = VorticityPlan(u, v, twin, fill_halos=fill_halos, mask_immersed=mask_immersed)
-    return zeta
+    return _remembering_field(_LOCS["zeta"], u.grid, "zeta",
+                              lambda twin: VorticityPlan(u, v, twin, fill_halos=fill_halos, mask_immersed=mask_immersed))
 
 
 def compute_(field):

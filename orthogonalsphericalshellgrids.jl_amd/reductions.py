@@ -25,6 +25,21 @@ def _bare(grid):
     return getattr(grid, "underlying_grid", grid)
 
 
+def _z_spec_values(grid):
+    """grid.z_spec as a Python list: the two ends of a regular interval, or the explicit faces"""
+    z = _bare(grid).z_spec
+    return z.flatten().tolist() if torch.is_tensor(z) else list(z)
+
+
+def _grid_table(grid, key, build, dtype, device):
+    """the device copy of the host table build(grid, dtype), made once per (grid, type, device) and kept with the grid under `key`"""
+    g = _bare(grid)
+    cache = g.__dict__.setdefault(key, {})
+    if (dtype, str(device)) not in cache:
+        cache[(dtype, str(device))] = build(g, dtype).to(dtype).to(device)
+    return cache[(dtype, str(device))]
+
+
 def _workspace(lib, n, geom, device):
     nbytes = int(lib.tpg_reduce_workspace_bytes(n, geom[0], geom[1], geom[2]))
     return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
@@ -134,7 +149,7 @@ def z_face_spacings(grid, dtype=None):
     that are exact in `dtype`."""
     g = _bare(grid)
     Nz = g.Nz
-    zz = g.z_spec.flatten().tolist() if torch.is_tensor(g.z_spec) else list(g.z_spec)
+    zz = _z_spec_values(g)
     if len(zz) == 2:
         d = torch.full((Nz,), (float(zz[1]) - float(zz[0])) / Nz, dtype=torch.float64)
     else:
@@ -143,14 +158,19 @@ def z_face_spacings(grid, dtype=None):
     return d.to(dtype or g.dtype).to(torch.float64)
 
 
-def _dz_f(grid, dtype, device):
-    """the device copy of z_face_spacings, built once per (grid, type) and kept with the grid"""
+def z_center_spacings(grid, dtype=None):
+    """Δzᵃᵃᶜ[k] for k = 1..Nz: the face-to-face spacing at centre k, computed in float64 from grid.z_spec and rounded ONCE to `dtype` (default:
+    the grid's), as z_face_spacings is.  A regular interval (z0, z1) gives (z1 - z0) / Nz at every level; explicit faces give the float64
+    differences of adjacent faces.  A float64 host tensor of values that are exact in `dtype`."""
     g = _bare(grid)
-    cache = g.__dict__.setdefault("_z_face_spacings", {})
-    key = (dtype, str(device))
-    if key not in cache:
-        cache[key] = z_face_spacings(g, dtype).to(dtype).to(device)
-    return cache[key]
+    Nz = g.Nz
+    zz = _z_spec_values(g)
+    if len(zz) == 2:
+        d = torch.full((Nz,), (float(zz[1]) - float(zz[0])) / Nz, dtype=torch.float64)
+    else:
+        f = torch.tensor([float(z) for z in zz], dtype=torch.float64)
+        d = f[1:Nz + 1] - f[0:Nz]
+    return d.to(dtype or g.dtype).to(torch.float64)
 
 
 def _metric(g, name, dtype, device):
@@ -184,7 +204,7 @@ class AdvectionTimescalePlan:
         ncc = None if counts is None else counts["cc"]
         with torch.cuda.device(device):
             dx, dy = _metric(g, "dx_fc", dtype, device), _metric(g, "dy_cf", dtype, device)
-            dz = _dz_f(g, dtype, device)
+            dz = _grid_table(g, "_z_face_spacings", z_face_spacings, dtype, device)
             self._out = torch.empty(1, dtype=torch.float64, device=device)
             ws = _workspace(lib, 1, geom, device)
         self._held = [u.data, v.data, w.data, dx, dy, dz, ncc, ws]
@@ -303,7 +323,7 @@ def summary(grid):
     g = _bare(grid)
     s = grid_summary(g)
     tx, ty, tz = (t.__name__.replace("Topology", "") for t in g.topology)
-    zz = g.z_spec.flatten().tolist() if torch.is_tensor(g.z_spec) else list(g.z_spec)
+    zz = _z_spec_values(g)
     z0, z1 = float(zz[0]), float(zz[-1])
     zline = (f"regularly spaced with Δz={_sig((z1 - z0) / g.Nz)}" if len(zz) == 2 else
              f"variably spaced with min(Δz)={_sig(min(b - a for a, b in zip(zz, zz[1:])))}, max(Δz)={_sig(max(b - a for a, b in zip(zz, zz[1:])))}")

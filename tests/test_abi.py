@@ -140,12 +140,17 @@ def test_product_has_no_cpu_path(osg):
         osg.TripolarGrid(osg.CPU(), size=(60, 30, 1))
 
 
-def test_missing_extension_fails_loudly(osg, monkeypatch, tmp_path):
-    """no silent fallback: without libtripolar_hip.so the binding raises"""
-    monkeypatch.setattr(osg._lib, "_lib", None)
-    monkeypatch.setattr(osg._lib, "LIB_PATH", str(tmp_path / "libtripolar_hip.so"))
-    with pytest.raises(ImportError, match="only backend"):
-        osg._lib.lib()
+@pytest.mark.parametrize("loader, handle, path", [
+    ("lib", "_lib", "LIB_PATH"), ("operators_lib", "_operators", "OPERATORS_LIB_PATH"), ("continuity_lib", "_continuity", "CONTINUITY_LIB_PATH"),
+    ("barotropic_lib", "_barotropic", "BAROTROPIC_LIB_PATH"), ("free_surface_lib", "_free_surface", "FREE_SURFACE_LIB_PATH")])
+def test_missing_extension_fails_loudly(osg, monkeypatch, tmp_path, loader, handle, path):
+    """no silent fallback: without its shared library a binding raises, and names the path it looked at"""
+    missing = str(tmp_path / os.path.basename(getattr(osg._lib, path)))
+    monkeypatch.setattr(osg._lib, handle, None)
+    monkeypatch.setattr(osg._lib, path, missing)
+    with pytest.raises(ImportError, match="only backend") as err:
+        getattr(osg._lib, loader)()
+    assert missing in str(err.value)
 
 
 def test_product_does_not_import_the_oracle():
