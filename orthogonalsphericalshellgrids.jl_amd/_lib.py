@@ -1,11 +1,11 @@
-"""ctypes binding of libtripolar_hip.so (include/tripolar_hip.h) and of the four operator libraries beside it
-(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h).
+"""ctypes binding of libtripolar_hip.so (include/tripolar_hip.h) and of the five operator libraries beside it
+(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
-status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic and free_surface.
+status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface and timestep.
 """
 import ctypes as C
 import os
@@ -137,6 +137,16 @@ FREE_SURFACE_SIGNATURES = {
     "tpg_free_surface_substep": (_i, [_vp] * 19 + [C.c_double] * 3 + [_i] * 6 + [_vp]),
 }
 
+# every symbol include/tripolar_hip_timestep.h declares (libtripolar_hip_timestep.so: the sixth library, no test build)
+TIMESTEP_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_timestep.so")
+TPG_AB2_EULER, TPG_AB2_STORE_PREVIOUS = 1, 2                 # flag bits of both calls
+TIMESTEP_SIGNATURES = {
+    "tpg_timestep_last_error": (C.c_char_p, []),
+    "tpg_ab2_step_velocities": (_i, [_vp] * 11 + [C.c_double] * 2 + [_i] + _geom + [_i, _i, _vp]),
+    "tpg_ab2_step_fields": (_i, [C.POINTER(_vp)] * 3 + [_i] + [C.c_double] * 2 + [_i] + _geom + [_i, _vp]),
+}
+
+
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
     handle = C.CDLL(path)
@@ -180,7 +190,8 @@ operators_lib, check_operators = _library("_operators", "OPERATORS_LIB_PATH", OP
 continuity_lib, check_continuity = _library("_continuity", "CONTINUITY_LIB_PATH", CONTINUITY_SIGNATURES, "tpg_continuity_last_error")
 barotropic_lib, check_barotropic = _library("_barotropic", "BAROTROPIC_LIB_PATH", BAROTROPIC_SIGNATURES, "tpg_barotropic_last_error")
 free_surface_lib, check_free_surface = _library("_free_surface", "FREE_SURFACE_LIB_PATH", FREE_SURFACE_SIGNATURES, "tpg_free_surface_last_error")
-OPERATOR_LIBRARIES = (operators_lib, continuity_lib, barotropic_lib, free_surface_lib)
+timestep_lib, check_timestep = _library("_timestep", "TIMESTEP_LIB_PATH", TIMESTEP_SIGNATURES, "tpg_timestep_last_error")
+OPERATOR_LIBRARIES = (operators_lib, continuity_lib, barotropic_lib, free_surface_lib, timestep_lib)
 
 
 def ft_of(dtype):
