@@ -33,5 +33,6 @@ from .barotropic import (BarotropicCorrectionPlan, BarotropicModePlan, barotropi
                          barotropic_mode_plan, column_depth_table, compute_barotropic_mode)
 from .free_surface import (SplitExplicitFreeSurface, SplitExplicitSubcyclePlan, split_explicit_subcycle_plan, split_explicit_substep)
 from .time_stepping import (Ab2StepPlan, Ab2VelocityStepPlan, ab2_step_fields, ab2_step_plan, ab2_step_velocities, ab2_velocity_step_plan)
+from .advection import TracerAdvectionPlan, tracer_advection_plan, tracer_advection_tendency
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

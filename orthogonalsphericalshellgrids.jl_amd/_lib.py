@@ -1,11 +1,12 @@
-"""ctypes binding of libtripolar_hip.so (include/tripolar_hip.h) and of the five operator libraries beside it
-(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h).
+"""ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
+(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency library (_advection.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
-status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface and timestep.
+status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep and
+advection.
 """
 import ctypes as C
 import os
@@ -146,6 +147,14 @@ TIMESTEP_SIGNATURES = {
     "tpg_ab2_step_fields": (_i, [C.POINTER(_vp)] * 3 + [_i] + [C.c_double] * 2 + [_i] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_advection.h declares (libtripolar_hip_advection.so: the seventh library, no test build)
+ADVECTION_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_advection.so")
+TPG_ADVECTION_CENTERED2 = 0                                  # `scheme` of tpg_tracer_advection_tendency: the only one built
+ADVECTION_SIGNATURES = {
+    "tpg_advection_last_error": (C.c_char_p, []),
+    "tpg_tracer_advection_tendency": (_i, [C.POINTER(_vp)] * 2 + [_i] + [_vp] * 8 + [C.c_double, _i] + _geom + [_i, _vp]),
+}
+
 
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
@@ -191,7 +200,9 @@ continuity_lib, check_continuity = _library("_continuity", "CONTINUITY_LIB_PATH"
 barotropic_lib, check_barotropic = _library("_barotropic", "BAROTROPIC_LIB_PATH", BAROTROPIC_SIGNATURES, "tpg_barotropic_last_error")
 free_surface_lib, check_free_surface = _library("_free_surface", "FREE_SURFACE_LIB_PATH", FREE_SURFACE_SIGNATURES, "tpg_free_surface_last_error")
 timestep_lib, check_timestep = _library("_timestep", "TIMESTEP_LIB_PATH", TIMESTEP_SIGNATURES, "tpg_timestep_last_error")
+advection_lib, check_advection = _library("_advection", "ADVECTION_LIB_PATH", ADVECTION_SIGNATURES, "tpg_advection_last_error")
 OPERATOR_LIBRARIES = (operators_lib, continuity_lib, barotropic_lib, free_surface_lib, timestep_lib)
+TENDENCY_LIBRARIES = (advection_lib,)                        # what produces the tendencies the AB2 step consumes
 
 
 def ft_of(dtype):
