@@ -18,28 +18,40 @@ using namespace tpgm;
 
 #define TPG_UNROLL _Pragma("unroll")
 
+// A Float64 literal of a one-element batch, pinned to a scalar register pair.  A literal with a non-zero low word needs a register; used
+// once, the compiler builds it in a VECTOR pair (two v_mov_b32) so that the fma can take its two-address form -- two VALU instructions per
+// coefficient.  From a scalar pair the three-address fma reads it as its one scalar operand.  Batches of two and more use every
+// coefficient more than once and get the scalar pair by themselves.
+template <int N> TPG_DEV double kc(double c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (N == 1) asm("" : "+s"(c));
+#endif
+    return c;
+}
+
 // ksin / kcos of x + y, elementwise (any N)
 template <int N> TPG_DEV void ksin_b(const double (&x)[N], const double (&y)[N], double (&out)[N])
 {
     double z[N], r[N], v[N];
     TPG_UNROLL for (int e = 0; e < N; ++e) z[e] = x[e] * x[e];
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], 2.75573137070700676789e-06);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], -1.98412698298579493134e-04);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], 8.33333333332248946124e-03);
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], kc<N>(1.58969099521155010221e-10), kc<N>(-2.50507602534068634195e-08));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(2.75573137070700676789e-06));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(-1.98412698298579493134e-04));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(8.33333333332248946124e-03));
     TPG_UNROLL for (int e = 0; e < N; ++e) v[e] = z[e] * x[e];
     TPG_UNROLL for (int e = 0; e < N; ++e)
-        out[e] = x[e] - ((z[e] * (0.5 * y[e] - v[e] * r[e]) - y[e]) - v[e] * -1.66666666666666324348e-01);
+        out[e] = x[e] - ((z[e] * (0.5 * y[e] - v[e] * r[e]) - y[e]) - v[e] * kc<N>(-1.66666666666666324348e-01));
 }
 template <int N> TPG_DEV void kcos_b(const double (&x)[N], const double (&y)[N], double (&out)[N])
 {
     double z[N], r[N];
     TPG_UNROLL for (int e = 0; e < N; ++e) z[e] = x[e] * x[e];
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], -2.75573143513906633035e-07);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], 2.48015872894767294178e-05);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], -1.38888888888741095749e-03);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], 4.16666666666666019037e-02);
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], kc<N>(-1.13596475577881948265e-11), kc<N>(2.08757232129817482790e-09));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(-2.75573143513906633035e-07));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(2.48015872894767294178e-05));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(-1.38888888888741095749e-03));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(4.16666666666666019037e-02));
     TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = z[e] * r[e];
     TPG_UNROLL for (int e = 0; e < N; ++e) {
         double hz = 0.5 * z[e];
@@ -61,14 +73,14 @@ template <int N> TPG_DEV void ksin0_b(const double (&x)[N], double (&out)[N])
 {
     double z[N], r[N], v[N];
     TPG_UNROLL for (int e = 0; e < N; ++e) z[e] = x[e] * x[e];
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], 2.75573137070700676789e-06);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], -1.98412698298579493134e-04);
-    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], 8.33333333332248946124e-03);
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], kc<N>(1.58969099521155010221e-10), kc<N>(-2.50507602534068634195e-08));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(2.75573137070700676789e-06));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(-1.98412698298579493134e-04));
+    TPG_UNROLL for (int e = 0; e < N; ++e) r[e] = fmaD(z[e], r[e], kc<N>(8.33333333332248946124e-03));
     TPG_UNROLL for (int e = 0; e < N; ++e) v[e] = z[e] * x[e];
     TPG_UNROLL for (int e = 0; e < N; ++e) {
         const double t = v[e] * r[e];
-        out[e] = x[e] - (z[e] * -t - v[e] * -1.66666666666666324348e-01);
+        out[e] = x[e] - (z[e] * -t - v[e] * kc<N>(-1.66666666666666324348e-01));
     }
 }
 
@@ -307,15 +319,15 @@ template <int N> TPG_DEV bool asin_small_b(const double (&x)[N], double (&out)[N
     double t[N], p[N], q[N];
     bool rare = false;
     TPG_UNROLL for (int e = 0; e < N; ++e) { t[e] = x[e] * x[e]; rare |= !(absD(x[e]) < 0.5); }
-    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], 3.47933107596021167570e-05, 7.91534994289814532176e-04);
-                                             q[e] = fmaD(t[e], 7.70381505559019352791e-02, -6.88283971605453293030e-01); }
-    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], p[e], -4.00555345006794114027e-02);
-                                             q[e] = fmaD(t[e], q[e], 2.02094576023350569471e+00); }
-    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], p[e], 2.01212532134862925881e-01);
-                                             q[e] = fmaD(t[e], q[e], -2.40339491173441421878e+00); }
-    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], p[e], -3.25565818622400915405e-01);
+    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], kc<N>(3.47933107596021167570e-05), kc<N>(7.91534994289814532176e-04));
+                                             q[e] = fmaD(t[e], kc<N>(7.70381505559019352791e-02), kc<N>(-6.88283971605453293030e-01)); }
+    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], p[e], kc<N>(-4.00555345006794114027e-02));
+                                             q[e] = fmaD(t[e], q[e], kc<N>(2.02094576023350569471e+00)); }
+    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], p[e], kc<N>(2.01212532134862925881e-01));
+                                             q[e] = fmaD(t[e], q[e], kc<N>(-2.40339491173441421878e+00)); }
+    TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], p[e], kc<N>(-3.25565818622400915405e-01));
                                              q[e] = fmaD(t[e], q[e], 1.0); }
-    TPG_UNROLL for (int e = 0; e < N; ++e) p[e] = fmaD(t[e], p[e], 1.66666666666666657415e-01);
+    TPG_UNROLL for (int e = 0; e < N; ++e) p[e] = fmaD(t[e], p[e], kc<N>(1.66666666666666657415e-01));
     TPG_UNROLL for (int e = 0; e < N; ++e) p[e] = t[e] * p[e];
     // q in (0.77, 1] for t < 0.25 and |p| <= 0.05 with p = 0 or |p| >= t/7 (t = x*x of a clamped sqrt: 0 or
     // >= 1e-40 here), so the unscaled division is exact-equivalent; lanes with |x| >= 0.5 or NaN are `rare`
@@ -324,45 +336,50 @@ template <int N> TPG_DEV bool asin_small_b(const double (&x)[N], double (&out)[N
 }
 
 // sind / cosd pairs for |x| < 360 (longitudes in [0,360), latitudes in [-90,90]: rem(x,360) = x)
-template <int N> TPG_DEV void sincosd_b(const double (&x)[N], double (&sn)[N], double (&cs)[N])
+// One ladder of threshold compares serves both functions.  With m = the number of sind's thresholds (>= 45, > 135, >= 225, > 315)
+// that r = |x| passes, d = 90 m - r, t = |d| and S = ksin, C = kcos of deg2rad(t):
+//    sind = sign(x) * { +S, +C, sign(d) S, -C, -S }[m]
+//    cosd =           { +C, sign(d) S, -C, (d > 0 ? -S : +S), +C }[m]
+// cosd's own ladder (> 45, >= 135, > 225, >= 315) counts differently only AT a threshold, where m is odd, its own count is even
+// and t = 45 for either: there cosd takes C, with the sign the table gives for sign(d) / d > 0 (r = 45: d = +45, +C; 135: d = -45,
+// -C; 225: d = +45, -C; 315: d = -45, +C).  m = 3: cosd = sign(r - 270) S, and r - 270 = -d except that it is +0 where d = +0
+// (r = 270, cosd = +0), hence "d > 0" and not the sign bit; d is never -0 (a difference of equal numbers is +0).
+// The factors +-1 are applied as an xor on the high word: x * +-1.0 is exact and only sets the sign (of a zero as well), so the bits
+// are those of the product for every non-NaN x.  All of it is checked bit for bit against the two-ladder form it replaces:
+// tests/test_cells_trims.py.
+// POS = true: the caller guarantees that no x has its sign bit set (the longitudes of the tile kernel, which leave fmod360_pos).
+template <int N, bool POS = false> TPG_DEV void sincosd_b(const double (&x)[N], double (&sn)[N], double (&cs)[N])
 {
-    // The octant logic is kept in booleans (lane masks in SGPRs, combined by scalar instructions) rather
-    // than in integer counters: m = number of thresholds passed, m & 1 = parity of the four compares,
-    // m >= 3 <=> third compare, m == 2 <=> second and not third, 90 m = a select among exact constants.
-    double h[N], l[N], S[N], C[N], r[N], d[N];
-    bool sodd[N], s_ge3[N], s_eq2[N], codd[N], c_eq1[N], c_eq2[N];
+    double h[N], l[N], S[N], C[N];
+    bool sC[N], cS[N];           // sind takes C / cosd takes S
+    int ws[N], wc[N];            // bit 31: sind / cosd is negated
     TPG_UNROLL for (int e = 0; e < N; ++e) {
-        r[e] = absD(x[e]);
-        const bool s1 = r[e] >= 45.0, s2 = r[e] > 135.0, s3 = r[e] >= 225.0, s4 = r[e] > 315.0;    // sind's octants
-        const bool c1 = r[e] > 45.0, c2 = r[e] >= 135.0, c3 = r[e] > 225.0, c4 = r[e] >= 315.0;    // cosd's octants
-        sodd[e] = (s1 != s2) != (s3 != s4); s_ge3[e] = s3; s_eq2[e] = s2 && !s3;
-        codd[e] = (c1 != c2) != (c3 != c4); c_eq1[e] = c1 && !c2; c_eq2[e] = c2 && !c3;
-        double m90 = 0.0;
-        m90 = s1 ? 90.0 : m90; m90 = s2 ? 180.0 : m90; m90 = s3 ? 270.0 : m90; m90 = s4 ? 360.0 : m90;
-        d[e] = m90 - r[e];
-        double t = absD(d[e]);
-        double hh = t * kDeg2Rad;
+        const double r = absD(x[e]);
+        const bool s1 = r >= 45.0, s2 = r > 135.0, s3 = r >= 225.0, s4 = r > 315.0;
+        int mh = 0;                                                        // high word of 90 m (the low words are zero)
+        mh = s1 ? 0x40568000 : mh; mh = s2 ? 0x40668000 : mh; mh = s3 ? 0x4070E000 : mh; mh = s4 ? 0x40768000 : mh;
+        const double d = __hiloint2double(mh, 0) - r;
+        const double t = absD(d);
+        const double hh = t * kDeg2Rad;
         l[e] = fmaD(t, kDeg2Rad, -hh) + t * kDeg2RadLo;
         h[e] = hh;
+        const int dh = __double2hiint(d);
+        const bool odd = (s1 != s2) != (s3 != s4), m1 = s1 && !s2, m2 = s2 && !s3, m3 = s3 && !s4;
+        sC[e] = odd;
+        cS[e] = odd && t != 45.0;
+        const int sneg = s3 ? (int)0x80000000 : 0;
+        ws[e] = m2 ? dh : sneg;
+        const int cneg = (m2 || (m3 && d > 0.0)) ? (int)0x80000000 : 0;
+        wc[e] = m1 ? dh : cneg;
+        if (!POS) ws[e] ^= __double2hiint(x[e]);
     }
     ksin_b<N>(h, l, S);
     kcos_b<N>(h, l, C);
     TPG_UNROLL for (int e = 0; e < N; ++e) {
-        const double sg = csign(1.0, x[e]), nsg = -sg;
-        const double dsg = csign(1.0, d[e]);
-        const double bs = sodd[e] ? C[e] : S[e];
-        const double f2 = dsg * sg;
-        double fs = sg;
-        fs = s_ge3[e] ? nsg : fs;
-        fs = s_eq2[e] ? f2 : fs;
-        sn[e] = fs * bs;
-        const double bc = codd[e] ? S[e] : C[e];
-        const double a1 = 90.0 - r[e], a3 = r[e] - 270.0;
-        const double arg = c_eq1[e] ? a1 : a3;
-        const double fodd = csign(1.0, arg);
-        const double feven = c_eq2[e] ? -1.0 : 1.0;
-        const double fc = codd[e] ? fodd : feven;
-        cs[e] = fc * bc;
+        const int slo = sC[e] ? __double2loint(C[e]) : __double2loint(S[e]), shi = sC[e] ? __double2hiint(C[e]) : __double2hiint(S[e]);
+        const int clo = cS[e] ? __double2loint(S[e]) : __double2loint(C[e]), chi = cS[e] ? __double2hiint(S[e]) : __double2hiint(C[e]);
+        sn[e] = __hiloint2double(shi ^ (ws[e] & (int)0x80000000), slo);
+        cs[e] = __hiloint2double(chi ^ (wc[e] & (int)0x80000000), clo);
     }
 }
 

@@ -512,15 +512,18 @@ __device__ __forceinline__ void points_pair(const GridK& g, const LaneConst& lc,
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     // lane 0 has no Face image (64 - 0); it is a west apron, whose Face points nobody reads: any finite chain will do
     const int srcF = face ? lane : (lane == 0 ? 63 : 64 - lane), srcC = face ? 63 - lane : lane;
-    const int sgF = __double2hiint(lc.aslF) ^ __double2hiint(lc.aclF), sgC = __double2hiint(lc.aslC) ^ __double2hiint(lc.aclC);
-    const int sgJc = __double2hiint(rt.shC), sgJf = __double2hiint(rt.shF);
-    const int sg[4] = { sgF ^ sgJc, sgC ^ sgJc, sgF ^ sgJf, sgC ^ sgJf };
+    // the sign of at1 as a word with bit 31 only: the lane's part (one per x-location) and the row's part (wave-uniform, scalar).  It is
+    // applied around the product -180/pi |at1| below -- (-c) (s |t|) = s ((-c) |t|) bit for bit, a product's sign is the xor of its
+    // factors' -- where |at1| is an operand modifier, the row's part rides on the constant and the lane's part is one xor per point
+    const int sgn = (int)0x80000000;
+    int sgJc = __double2hiint(rt.shC) & sgn, sgJf = __double2hiint(rt.shF) & sgn;
+    int sgF = (__double2hiint(lc.aslF) ^ __double2hiint(lc.aclF)) & sgn, sgC = (__double2hiint(lc.aslC) ^ __double2hiint(lc.aclC)) & sgn;
+    asm volatile("" : "+v"(sgF), "+v"(sgC), "+s"(sgJc), "+s"(sgJf));     // keeps the parts masked: re-associated to (a ^ b) & m, every point pays the mask again
     double at1[4], sp[2], cp[2];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int src = (k == 0 || k == 2) ? srcF : srcC;
-        const double t = L[3 * k + 0][p][src];
-        at1[k] = __hiloint2double((__double2hiint(t) & 0x7fffffff) | (sg[k] & (int)0x80000000), __double2loint(t));
+        at1[k] = L[3 * k + 0][p][src];
         s.phi[k] = L[3 * k + 1][p][src];
         s.ca[k] = L[3 * k + 2][p][src];
     }
@@ -529,16 +532,29 @@ __device__ __forceinline__ void points_pair(const GridK& g, const LaneConst& lc,
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();                                                       // the records go into these rows next
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // |-180/pi at1 + (+-90)| <= 180 + 2 ulp, so with |fplp90| < 179 (wave-uniform; the default pole longitude gives 160) |l| < 360 and the
+    // first fmod is the identity: csign(|l| - 0, l) = l
+    const bool lsmall = (__double2hiint(g.fplp90) & 0x7fffffff) < 0x40666000;     // |fplp90| < 179 on the high word: a scalar compare
+    const double cJc = __hiloint2double(__double2hiint(-kC180Pi) ^ sgJc, __double2loint(-kC180Pi));      // -180/pi with the row's sign: scalar
+    const double cJf = __hiloint2double(__double2hiint(-kC180Pi) ^ sgJf, __double2loint(-kC180Pi));
+    double l[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        double l = -kC180Pi * at1[k];                          // :77 (no pole below row Ny)
-        l += lc.hemi;                                          // :82
-        l += g.fplp90;                                         // :86
-        s.lam[k] = tpgb::fmod360_pos(tpgb::fmod360_small(l) + 360.0);     // :87
+        const double m = ((k < 2) ? cJc : cJf) * absD(at1[k]);  // :77 (no pole below row Ny)
+        l[k] = __hiloint2double(__double2hiint(m) ^ ((k == 0 || k == 2) ? sgF : sgC), __double2loint(m));
+        l[k] += lc.hemi;                                       // :82
+        l[k] += g.fplp90;                                      // :86
         s.a[k] = s.phi[k] * kDeg2Rad;
     }
+    if (lsmall) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s.lam[k] = tpgb::fmod360_pos(l[k] + 360.0);                            // :87
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s.lam[k] = tpgb::fmod360_pos(tpgb::fmod360_small(l[k]) + 360.0);       // :87
+    }
     double lon[2] = { s.lam[1], s.lam[2] }, sl[2], cl[2];
-    tpgb::sincosd_b<2>(lon, sl, cl);
+    tpgb::sincosd_b<2, true>(lon, sl, cl);                               // POS: lam = fmod360_pos(y + 360), |y| < 360, lies in [+0, 360] -- sign bit clear
     s.X[0] = cl[0] * cp[0]; s.Y[0] = sl[0] * cp[0]; s.Z[0] = sp[0];      // CC
     s.X[1] = cl[1] * cp[1]; s.Y[1] = sl[1] * cp[1]; s.Z[1] = sp[1];      // FF
 }
@@ -751,24 +767,35 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
         // eight haversines, Dy_ff = hav(FC(i,s), FC(i,s-1)), for every row of the tile from LDS (two rows at a time)
         if (col_emit) {
             double (*L)[R][64] = lds.v;
+            // rows in pairs while two are left, then the odd one alone (a whole tile: three pairs and row R - 1), as the cell rows do
+            // for Dy_cf: no haversine is evaluated twice
+            int r = 1;
 #pragma unroll 1
-            for (int r = 1; r < R; r += 2) {
+            for (; r + 1 < R && s0 + r + 1 <= g.jm_hi; r += 2) {
                 const int sa = s0 + r, sb = sa + 1;
-                if (sa > g.jm_hi) break;
-                const bool two = (r + 1 < R) && sb <= g.jm_hi;
-                const int rb = two ? r + 1 : r;
                 double dd2[2];
 #if TPG_CELLS_PROBE == 1
                 dd2[0] = dd2[1] = L[L_FC + 0][r][lane];
 #else
                 Nb X[2] = { Nb{ L[L_FC + 0][r][lane], L[L_FC + 1][r][lane], L[L_FC + 2][r][lane] },
-                            Nb{ L[L_FC + 0][rb][lane], L[L_FC + 1][rb][lane], L[L_FC + 2][rb][lane] } };
-                Nb Y[2] = { Nb{ L[L_FC + 0][r - 1][lane], L[L_FC + 1][r - 1][lane], L[L_FC + 2][r - 1][lane] },
-                            Nb{ L[L_FC + 0][rb - 1][lane], L[L_FC + 1][rb - 1][lane], L[L_FC + 2][rb - 1][lane] } };
+                            Nb{ L[L_FC + 0][r + 1][lane], L[L_FC + 1][r + 1][lane], L[L_FC + 2][r + 1][lane] } };
+                Nb Y[2] = { Nb{ L[L_FC + 0][r - 1][lane], L[L_FC + 1][r - 1][lane], L[L_FC + 2][r - 1][lane] }, X[0] };
                 hav_batch<2>(X, Y, Rad, dd2);
 #endif
                 if (sa >= g.jm_lo) TPG_EMIT(TPG_DY_FF, rowoff(sa), dd2[0]);
-                if (two && sb >= g.jm_lo) TPG_EMIT(TPG_DY_FF, rowoff(sb), dd2[1]);
+                if (sb >= g.jm_lo) TPG_EMIT(TPG_DY_FF, rowoff(sb), dd2[1]);
+            }
+            if (r < R && s0 + r <= g.jm_hi) {
+                const int sa = s0 + r;
+                double dd1[1];
+#if TPG_CELLS_PROBE == 1
+                dd1[0] = L[L_FC + 0][r][lane];
+#else
+                Nb X[1] = { Nb{ L[L_FC + 0][r][lane], L[L_FC + 1][r][lane], L[L_FC + 2][r][lane] } };
+                Nb Y[1] = { Nb{ L[L_FC + 0][r - 1][lane], L[L_FC + 1][r - 1][lane], L[L_FC + 2][r - 1][lane] } };
+                hav_batch<1>(X, Y, Rad, dd1);
+#endif
+                if (sa >= g.jm_lo) TPG_EMIT(TPG_DY_FF, rowoff(sa), dd1[0]);
             }
         }
     } else if (active_row && s >= g.jm_lo) {                                 // idle rows have no phase 2 (wave-uniform)
