@@ -10,7 +10,8 @@ HydrostaticFreeSurfaceModel(; grid, free_surface = SplitExplicitFreeSurface(grid
   w from continuity.
 
 A 1-degree tripolar grid with 10 unevenly spaced levels under an ImmersedBoundaryGrid whose bottom masks the two grid poles and the far south.
-The tendencies stand in for a model's (advection, Coriolis and the pressure gradient are out of scope): a steady zonal wind stress spread
+The tendencies stand in for a model's (the advective ones are examples/bickley_model_step.py's; Coriolis and the pressure gradient are out
+of scope): a steady zonal wind stress spread
 over the upper 70 m.  Five plans built once, then per step: AB2 -> mode -> sub-cycle -> correction -> w.  The step runs eagerly from a saved
 start, then the same chain is captured into ONE graph and replayed from the same start: the script prints that the two agree bit for bit.
 Run on an MI355X:  python examples/ab2_split_explicit_step.py

@@ -25,7 +25,7 @@ from .distributed import (LoopbackMailbox, PendingExchange, RcclComm, check_band
 from .geometry import convert_to_latlong_frame, convert_to_native_frame, nonorthogonality_angle
 from .reductions import (AdvectionTimescalePlan, ExtremaPlan, TimeStepWizard, advection_timescale_plan, cell_advection_timescale,
                          extrema_plan, field_extrema, grid_summary, maximum, minimum, minimum_xspacing, minimum_yspacing, summary,
-                         z_face_spacings)
+                         z_all_face_spacings, z_face_spacings)
 from .operators import VerticalVorticityField, VorticityPlan, compute_, vertical_vorticity, vorticity_plan
 from .continuity import (ContinuityPlan, HorizontalDivergenceField, compute_w_from_continuity, continuity_plan, horizontal_divergence,
                          z_center_spacings)
@@ -34,5 +34,6 @@ from .barotropic import (BarotropicCorrectionPlan, BarotropicModePlan, barotropi
 from .free_surface import (SplitExplicitFreeSurface, SplitExplicitSubcyclePlan, split_explicit_subcycle_plan, split_explicit_substep)
 from .time_stepping import (Ab2StepPlan, Ab2VelocityStepPlan, ab2_step_fields, ab2_step_plan, ab2_step_velocities, ab2_velocity_step_plan)
 from .advection import TracerAdvectionPlan, tracer_advection_plan, tracer_advection_tendency
+from .momentum import MomentumAdvectionPlan, momentum_advection_plan, momentum_advection_tendency
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

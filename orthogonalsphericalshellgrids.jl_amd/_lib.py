@@ -1,12 +1,13 @@
 """ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
-(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency library (_advection.h).
+(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency libraries (_advection.h,
+_momentum.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
-status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep and
-advection.
+status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep,
+advection and momentum.
 """
 import ctypes as C
 import os
@@ -155,6 +156,14 @@ ADVECTION_SIGNATURES = {
     "tpg_tracer_advection_tendency": (_i, [C.POINTER(_vp)] * 2 + [_i] + [_vp] * 8 + [C.c_double, _i] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_momentum.h declares (libtripolar_hip_momentum.so: the eighth library, no test build)
+MOMENTUM_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_momentum.so")
+TPG_MOMENTUM_ENSTROPHY_CONSERVING = 0                        # `scheme` of tpg_momentum_advection_tendency: the only one built
+MOMENTUM_SIGNATURES = {
+    "tpg_momentum_last_error": (C.c_char_p, []),
+    "tpg_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double, _i] + _geom + [_i, _vp]),
+}
+
 
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
@@ -202,7 +211,8 @@ free_surface_lib, check_free_surface = _library("_free_surface", "FREE_SURFACE_L
 timestep_lib, check_timestep = _library("_timestep", "TIMESTEP_LIB_PATH", TIMESTEP_SIGNATURES, "tpg_timestep_last_error")
 advection_lib, check_advection = _library("_advection", "ADVECTION_LIB_PATH", ADVECTION_SIGNATURES, "tpg_advection_last_error")
 OPERATOR_LIBRARIES = (operators_lib, continuity_lib, barotropic_lib, free_surface_lib, timestep_lib)
-TENDENCY_LIBRARIES = (advection_lib,)                        # what produces the tendencies the AB2 step consumes
+momentum_lib, check_momentum = _library("_momentum", "MOMENTUM_LIB_PATH", MOMENTUM_SIGNATURES, "tpg_momentum_last_error")
+TENDENCY_LIBRARIES = (advection_lib, momentum_lib)                       # what produces the tendencies the AB2 step consumes
 
 
 def ft_of(dtype):

@@ -158,6 +158,21 @@ def z_face_spacings(grid, dtype=None):
     return d.to(dtype or g.dtype).to(torch.float64)
 
 
+def z_all_face_spacings(grid, dtype=None):
+    """Δzᵃᵃᶠ[k] for k = 1..Nz+1: z_face_spacings with the top face, whose centre above is a halo centre as the centre below face 1 is (the
+    vertical terms of the momentum tendency difference u and v across every face of the interior).  The first Nz values are
+    z_face_spacings' bit for bit; the same float64 arithmetic, rounded ONCE to `dtype`.  A float64 host tensor of values exact in `dtype`."""
+    g = _bare(grid)
+    Nz = g.Nz
+    zz = _z_spec_values(g)
+    if len(zz) == 2:
+        d = torch.full((Nz + 1,), (float(zz[1]) - float(zz[0])) / Nz, dtype=torch.float64)
+    else:
+        _, _, c = _z_coordinate(zz, Nz, 1, torch.float64, "cpu")         # centres k = 0 .. Nz+1
+        d = c[1:Nz + 2] - c[0:Nz + 1]
+    return d.to(dtype or g.dtype).to(torch.float64)
+
+
 def z_center_spacings(grid, dtype=None):
     """Δzᵃᵃᶜ[k] for k = 1..Nz: the face-to-face spacing at centre k, computed in float64 from grid.z_spec and rounded ONCE to `dtype` (default:
     the grid's), as z_face_spacings is.  A regular interval (z0, z1) gives (z1 - z0) / Nz at every level; explicit faces give the float64
