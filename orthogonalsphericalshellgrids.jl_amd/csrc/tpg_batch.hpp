@@ -18,6 +18,18 @@ using namespace tpgm;
 
 #define TPG_UNROLL _Pragma("unroll")
 
+// Instrument of tools/cells_ledger.py (scratch builds only: make GRID_FLAGS=-DTPG_CELLS_NO_FALLBACK=1, in the style of TPG_CELLS_PROBE):
+// no batch function reports a rare argument, so the compiler deletes every scalar fallback and what is left of a kernel is its main
+// path alone, readable instruction by instruction.  Results are WRONG by design; never built into a library that a test or the bench loads.
+#ifndef TPG_CELLS_NO_FALLBACK
+#define TPG_CELLS_NO_FALLBACK 0
+#endif
+#if TPG_CELLS_NO_FALLBACK
+#define TPG_RARE(r) false
+#else
+#define TPG_RARE(r) (r)
+#endif
+
 // A Float64 literal of a one-element batch, pinned to a scalar register pair.  A literal with a non-zero low word needs a register; used
 // once, the compiler builds it in a VECTOR pair (two v_mov_b32) so that the fma can take its two-address form -- two VALU instructions per
 // coefficient.  From a scalar pair the three-address fma reads it as its one scalar operand.  Batches of two and more use every
@@ -89,7 +101,7 @@ template <int N> TPG_DEV bool sin_small_b(const double (&x)[N], double (&out)[N]
     bool rare = false;
     TPG_UNROLL for (int e = 0; e < N; ++e) rare |= !(absD(x[e]) <= kPio4Hi);
     ksin0_b<N>(x, out);
-    return rare;
+    return TPG_RARE(rare);
 }
 
 // cos(a) through the first Cody-Waite step for every argument (n = 0 reproduces the direct
@@ -123,7 +135,7 @@ template <int N> TPG_DEV bool cos_b(const double (&a)[N], double (&out)[N])
         const double nv = -v;
         out[e] = ((n + 1) & 2) ? nv : v;
     }
-    return rare;
+    return TPG_RARE(rare);
 }
 
 // cos(a) for a = deg2rad(latitude), |a| <= pi/2 (+ rounding): the Cody-Waite quotient n = rint(a 2/pi) is -1, 0 or +1, so the
@@ -153,7 +165,7 @@ template <int N> TPG_DEV bool cos_lat_b(const double (&a)[N], double (&out)[N])
         const double nv = -v;
         out[e] = (fn[e] > 0.0) ? nv : v;
     }
-    return rare;
+    return TPG_RARE(rare);
 }
 
 // atan(x), all x (finite, +-Inf; NaN -> NaN).  The scalar early-outs are redundant value-wise:
@@ -242,14 +254,31 @@ TPG_DEV void atan_table_init(double* tab, int tid)
 // value-equivalence of dropping the msun early-outs).  p = 0 on the last interval: the numerator
 // uses min(ax, 2^1000) so that an infinite argument (y/x at x = +-0) still gives 0*ax - 1 = -1.
 // FINITE = true: the caller guarantees finite arguments (e.g. sqrt(x^2 + y^2)) and the clamp is skipped.
-template <int N, bool FINITE = false> TPG_DEV void atan_tab_b(const double (&x)[N], double (&out)[N], const double* tab)
+// ABS = true: returns atan(|x|) = |atan(x)|, the value before the copysign: r = hi - ((t s - lo) - t) has its sign bit clear for every
+// non-NaN x (hi >= 0.46 > |t| (1 + s) on the four reduced intervals; on the direct one r = 0 - (t s - t) with 0 <= t s <= t, and
+// t = +0 gives 0 - ((0 - 0) - 0) = +0).  For callers that take |atan| anyway, or whose argument is never negative.
+template <int N, bool FINITE = false, bool ABS = false> TPG_DEV void atan_tab_b(const double (&x)[N], double (&out)[N], const double* tab)
 {
     double t[N], hi[N], lo[N], s[N];
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the LUT's LDS address less the bias of u, as ONE scalar (the table is the wave's own): the clamp runs on the unbiased word and the
+    // byte's address is one v_add_u32.  Left to itself the compiler adds the table's address first and the negative constant, which no
+    // DS offset field can hold, second: two v_add_u32 per atan.
+    typedef const unsigned char __attribute__((address_space(3))) lds_cbyte;
+    unsigned lut0 = (unsigned)(uintptr_t)(lds_cbyte*)reinterpret_cast<const unsigned char*>(tab) + (8u * TPG_ATAN_ROWS_DOUBLES - 0x7FB7u);
+    asm("" : "+s"(lut0));
+#endif
     TPG_UNROLL for (int e = 0; e < N; ++e) {
         const double ax = absD(x[e]);
+#if defined(__HIP_DEVICE_COMPILE__)
+        unsigned m = __builtin_amdgcn_ubfe((unsigned)__double2hiint(x[e]), 15u, 16u);               // bits 15..30 of the high word: sign dropped
+        m = m < 0x7FB7u ? 0x7FB7u : (m > 0x7FB7u + 80u ? 0x7FB7u + 80u : m);
+        const unsigned off = *(lds_cbyte*)(uintptr_t)(lut0 + m);                                     // bytes
+#else
         int u = (int)__builtin_amdgcn_ubfe((unsigned)__double2hiint(x[e]), 15u, 16u) - 0x7FB7;     // bits 15..30 of the high word: sign dropped
         u = u < 0 ? 0 : (u > 80 ? 80 : u);
         const unsigned off = reinterpret_cast<const unsigned char*>(tab + TPG_ATAN_ROWS_DOUBLES)[u];   // bytes
+#endif
         const AtanRow row = *reinterpret_cast<const AtanRow*>(reinterpret_cast<const char*>(tab) + off);
         hi[e] = row.hi; lo[e] = row.lo;
         const double axn = (!FINITE && ax > 0x1p1000) ? 0x1p1000 : ax;      // NaN stays NaN (and selects the direct row)
@@ -280,18 +309,25 @@ template <int N, bool FINITE = false> TPG_DEV void atan_tab_b(const double (&x)[
     TPG_UNROLL for (int e = 0; e < N; ++e) {
         const double ts = t[e] * s[e];
         const double r = hi[e] - ((ts - lo[e]) - t[e]);
-        out[e] = csign(r, x[e]);
+        out[e] = ABS ? r : csign(r, x[e]);
     }
 }
 
 // atan(x) for |x| < 0.4375: the msun "direct" branch only (no argument reduction, no division).
 // The eight spherical-triangle tangents of a cell are O(cell area) ~ 1e-6, so this is their path.
 // rare: some |x| >= 0.4375 (or NaN) -> caller uses atan_b.
-template <int N> TPG_DEV bool atan_small_b(const double (&x)[N], double (&out)[N])
+// POS = true (the tile kernel's form): the fast path takes +0 <= x < 0.4375 only, as ONE unsigned compare of the high word (0.4375 has a
+// zero low word; a set sign bit or a NaN's exponent make the word large), so it needs neither |x| nor the copysign of the result: t = x,
+// and t - t s >= +0 is the result.  A negative tangent -- a triangle whose denominator 1 + a.b + b.c + a.c is negative: larger than a
+// hemisphere -- is `rare` in this form and goes through atan_b, which gives the same bits (both equal tpgm::atanD).
+template <int N, bool POS = false> TPG_DEV bool atan_small_b(const double (&x)[N], double (&out)[N])
 {
     double t[N], z[N], w[N], s1[N], s2[N];
     bool rare = false;
-    TPG_UNROLL for (int e = 0; e < N; ++e) { t[e] = absD(x[e]); rare |= !(t[e] < 0.4375); }
+    TPG_UNROLL for (int e = 0; e < N; ++e) {
+        if (POS) { t[e] = x[e]; rare |= !((unsigned)__double2hiint(x[e]) < 0x3FDC0000u); }
+        else     { t[e] = absD(x[e]); rare |= !(t[e] < 0.4375); }
+    }
     TPG_UNROLL for (int e = 0; e < N; ++e) { z[e] = t[e] * t[e]; w[e] = z[e] * z[e]; }
     TPG_UNROLL for (int e = 0; e < N; ++e) { s1[e] = fmaD(w[e], 1.62858201153657823623e-02, 4.97687799461593236017e-02);
                                              s2[e] = fmaD(w[e], -3.65315727442169155270e-02, -5.83357013379057348645e-02); }
@@ -306,19 +342,19 @@ template <int N> TPG_DEV bool atan_small_b(const double (&x)[N], double (&out)[N
     TPG_UNROLL for (int e = 0; e < N; ++e) {
         const double sm = z[e] * s1[e] + s2[e];
         const double r = t[e] - t[e] * sm;
-        out[e] = csign(r, x[e]);
+        out[e] = POS ? r : csign(r, x[e]);
     }
-    return rare;
+    return TPG_RARE(rare);
 }
 
 // asin(x) for |x| < 0.5.  tpgm::asinD returns x for |x| < 2^-26: x + x (p/q) with p/q ~ x^2/6
 // rounds to x there.  rare: some |x| >= 0.5 (edges longer than 60 degrees: the overwritten row
 // j = 1, toy grids) -> caller uses tpgm::asinD.
-template <int N> TPG_DEV bool asin_small_b(const double (&x)[N], double (&out)[N])
+// asin_small_poly_b: the evaluation alone, for a caller that decides the domain by a test of its own (asin_sqrt_b below).
+template <int N> TPG_DEV void asin_small_poly_b(const double (&x)[N], double (&out)[N])
 {
     double t[N], p[N], q[N];
-    bool rare = false;
-    TPG_UNROLL for (int e = 0; e < N; ++e) { t[e] = x[e] * x[e]; rare |= !(absD(x[e]) < 0.5); }
+    TPG_UNROLL for (int e = 0; e < N; ++e) t[e] = x[e] * x[e];
     TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], kc<N>(3.47933107596021167570e-05), kc<N>(7.91534994289814532176e-04));
                                              q[e] = fmaD(t[e], kc<N>(7.70381505559019352791e-02), kc<N>(-6.88283971605453293030e-01)); }
     TPG_UNROLL for (int e = 0; e < N; ++e) { p[e] = fmaD(t[e], p[e], kc<N>(-4.00555345006794114027e-02));
@@ -332,6 +368,34 @@ template <int N> TPG_DEV bool asin_small_b(const double (&x)[N], double (&out)[N
     // q in (0.77, 1] for t < 0.25 and |p| <= 0.05 with p = 0 or |p| >= t/7 (t = x*x of a clamped sqrt: 0 or
     // >= 1e-40 here), so the unscaled division is exact-equivalent; lanes with |x| >= 0.5 or NaN are `rare`
     TPG_UNROLL for (int e = 0; e < N; ++e) out[e] = x[e] + x[e] * tpgm::div_nr(p[e], q[e]);
+}
+template <int N> TPG_DEV bool asin_small_b(const double (&x)[N], double (&out)[N])
+{
+    bool rare = false;
+    TPG_UNROLL for (int e = 0; e < N; ++e) rare |= !(absD(x[e]) < 0.5);
+    asin_small_poly_b<N>(x, out);
+    return TPG_RARE(rare);
+}
+
+// asin(min(sqrt(h), 1)), the tail of a haversine (h = 0 or >= ~1e-34: squares of half-differences of O(1) doubles), on the unscaled
+// square root.  ONE test decides everything that derives from h: the unscaled square root of h = +-0 is NaN (rsq = +-Inf, 0 * Inf), of a
+// NaN or a negative h as well, and r < 0.5 is false for a NaN.  So r < 0.5 says that h > 0 (sqrt_nr is in its domain), that min(r, 1) = r
+// (no clamp) and that r lies in the fast domain of asin.  (Before: h == 0 with a patch of the square root, min(r, 1) as a v_min_f64 and
+// asin_small_b's own |x| < 0.5 -- every element that took the patch or the scalar asin then fails the one test now.)
+// The fallback evaluates the three as the reference has them: coincident points (pole-adjacent edges), edges longer than 60 degrees (the
+// overwritten row j = 1, toy grids), NaN.  Returns whether it ran (per lane).
+template <int N> TPG_DEV bool asin_sqrt_b(const double (&h)[N], double (&out)[N])
+{
+    double rt[N];
+    bool rare = false;
+    TPG_UNROLL for (int e = 0; e < N; ++e) { rt[e] = sqrt_nr<true>(h[e]); rare |= TPG_RARE(!(rt[e] < 0.5)); }
+    asin_small_poly_b<N>(rt, out);
+    if (rare) {
+        TPG_UNROLL for (int e = 0; e < N; ++e) {
+            const double r = sqrt_nr(h[e]);
+            out[e] = asinD(!(r >= 1.0) ? r : 1.0);      // min(r, 1) that keeps a NaN, as the reference's
+        }
+    }
     return rare;
 }
 
@@ -407,10 +471,12 @@ template <int N> TPG_DEV bool sincosd_lat_b(const double (&x)[N], double (&sn)[N
     kcos_b<N>(h, l, C);
     TPG_UNROLL for (int e = 0; e < N; ++e) {
         const double bs = s1[e] ? C[e] : S[e];
-        sn[e] = csign(1.0, x[e]) * bs;
+        // sign(x) * bs as a copysign: bs = ksin / kcos of deg2rad(t), 0 <= t <= 45, has its sign bit clear (ksin(+0, +0) = +0), and the
+        // product with +-1.0 is exact -- it sets the sign and nothing else.  (|x| > 90 or NaN: `rare`, the caller discards this)
+        sn[e] = csign(bs, x[e]);
         cs[e] = c1[e] ? S[e] : C[e];
     }
-    return rare;
+    return TPG_RARE(rare);
 }
 
 // fmod(x, 360) for 0 <= x < 720 (the second application in ((l % 360) + 360) % 360: l % 360 is in (-360, 360))

@@ -279,14 +279,22 @@ __device__ __forceinline__ void put(const OutPtrs& o, int q, long long off, doub
 // The tile kernel addresses its stores as (uniform base pointer) + (32-bit BYTE offset in a VGPR): the saddr form of
 // global_store takes exactly that, so the 20 stores of a cell share two offset registers instead of each paying a 64-bit
 // v_lshl_add_u64 for its own address (round 3).  Valid while one array is smaller than 4 GiB -- the launcher checks.
-template <typename T, bool NT = false>
+template <typename T, bool NT = false, bool PIN = true>
 __device__ __forceinline__ void put32(const OutPtrs& o, int q, unsigned boff, double v)
 {
     // the empty asm keeps the zero-extension of the offset next to its store: hoisted and shared as a 64-bit pair, it would no
     // longer match the saddr addressing pattern and every store would pay a 64-bit add again
-    asm volatile("" : "+v"(boff));
+    if (PIN) asm volatile("" : "+v"(boff));
     T* p = reinterpret_cast<T*>(static_cast<char*>(o.p[q]) + boff);
     if (NT) __builtin_nontemporal_store((T)v, p); else *p = (T)v;
+}
+// The asm of put32 costs a v_mov_b32 per store whose offset is used again afterwards (the operand is read-write, so the compiler copies
+// it first).  A run of stores in ONE basic block needs one pinned copy only: the zero-extension cannot leave the block without passing
+// the asm, and inside the block every store still selects base + zext(offset).  pin_off + put32<T, NT, false> is that form.
+__device__ __forceinline__ unsigned pin_off(unsigned boff)
+{
+    asm volatile("" : "+v"(boff));
+    return boff;
 }
 
 // ---- K1: interior cells ------------------------------------------------------------------------
@@ -484,9 +492,10 @@ __device__ __forceinline__ void points_pair(const GridK& g, const LaneConst& lc,
         // then take the FINITE form for every lane (no clamp of the argument; a NaN from div_nr(y, 0) just flows through the discarded lane).
         bool zerox = false;
 #pragma unroll
-        for (int m = 0; m < 2; ++m) { q[m] = div_nr(y[m], x[m]); zerox |= x[m] == 0.0; rr[m] = sqrt_nr<true>(y[m] * y[m] + x[m] * x[m]);   /* > 0: no pole below row Ny */ }
-        tpgb::atan_tab_b<2, true>(q, at1, atab);
-        tpgb::atan_tab_b<2, true>(rr, at2, atab);
+        for (int m = 0; m < 2; ++m) { q[m] = div_nr(y[m], x[m]); zerox |= TPG_RARE(x[m] == 0.0); rr[m] = sqrt_nr<true>(y[m] * y[m] + x[m] * x[m]);   /* > 0: no pole below row Ny */ }
+        // the ABS form, no copysign: only |at1| is used (its sign is rebuilt after the exchange, below), and rr > 0
+        tpgb::atan_tab_b<2, true, true>(q, at1, atab);
+        tpgb::atan_tab_b<2, true, true>(rr, at2, atab);
         if (zerox) {
 #pragma unroll
             for (int m = 0; m < 2; ++m)
@@ -568,7 +577,7 @@ __device__ __forceinline__ int wrap_col(int v, int Nx)
     return v;
 }
 
-// general rows (row Ny: fold, substitution, pole; row 0: zero south halo) through coord()
+// general rows (row Ny: fold, substitution, pole; any row when |fplp90| > 360) through coord()
 __device__ __noinline__ void points_general(const GridK& g, int i, int jc, int jf, Step4& s)
 {
     Pt fc = make_pt(g, 1, 0, i, jc), cf = make_pt(g, 0, 1, i, jf);
@@ -597,19 +606,29 @@ __device__ __noinline__ void points_general(const GridK& g, int i, int jc, int j
 // 31 / 63 east aprons, lanes 1-30 and 33-62 emit: (R-1)/R x 60/64 of the lanes.  The cells f1 .. f1 + Nx/2 - 1 and
 // their images partition 1..Nx, so tiles_x = ceil((Nx/2) / 30).  The Center image of lane l's column sits in lane
 // 63 - l and the Face image in lane 64 - l: phase 1 evaluates each pair's point chains once (points_pair).
-// A wave owns one point row, so the special rows (0, Ny) and |fplp90| > 360 are a wave-uniform branch to coord(),
-// unpaired: every lane evaluates its own column.
+// A wave owns one point row, so the special row Ny and |fplp90| > 360 are a wave-uniform branch to coord(),
+// unpaired: every lane evaluates its own column.  (Row 0 used to go there as well; now only its two Center-y points are special.)
 // Same arithmetic as k_cells for every value: bit-identical results.
 template <int R> struct TileLds { double v[18][R][64]; };
 enum { L_FC = 0, L_CC = 3, L_FF = 9, L_CF = 15 };    // field bases: FC(lam,a,ca) CC(lam,a,ca,X,Y,Z) FF(6) CF(3)
+
+// An LDS address in a VGPR that the compiler cannot see through: reads through it keep it as their base register and put everything
+// else into the immediate offset (see phase 2 of k_cells_tile).
+typedef const double __attribute__((address_space(3))) lds_cdouble;
+__device__ __forceinline__ lds_cdouble* lds_base(const double* p)
+{
+    unsigned a = (unsigned)(uintptr_t)(lds_cdouble*)p;
+    asm volatile("" : "+v"(a));
+    return (lds_cdouble*)(uintptr_t)a;
+}
+struct LdsBase { lds_cdouble* p; int plane; };     // the base and the plane of TileLds it points into
 
 // N haversines at once: x = first argument, y = second, each {lambda, deg2rad(phi), cos}; the same
 // operation sequence as hav() with the batch forms (rare arguments fall back to the scalar functions)
 template <int N>
 __device__ __forceinline__ void hav_batch(const Nb (&X)[N], const Nb (&Y)[N], double Rad, double (&d)[N])
 {
-    double hp[N], hl[N], s1[N], s2[N], hh[N], rt[N], rm[N], as[N];
-    bool zero = false;
+    double hp[N], hl[N], s1[N], s2[N], hh[N], as[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) {
         // (d lambda * deg2rad) / 2 as ONE product with deg2rad / 2: halving is exact and rounding is scale-invariant (no underflow:
@@ -626,26 +645,8 @@ __device__ __forceinline__ void hav_batch(const Nb (&X)[N], const Nb (&Y)[N], do
         for (int e = 0; e < N; ++e) s2[e] = sinD(hl[e]);
     }
 #pragma unroll
-    for (int e = 0; e < N; ++e) {
-        double h = s1[e] * s1[e] + X[e].ca * Y[e].ca * (s2[e] * s2[e]);
-        hh[e] = h;
-        zero |= h == 0.0;
-        rt[e] = sqrt_nr<true>(h);                 // h = 0 or >= ~1e-34 (squares of half-differences of O(1) doubles); h = 0 patched below
-    }
-    if (zero) {                                   // coincident points (pole-adjacent edges): the unscaled square root needs x > 0
-#pragma unroll
-        for (int e = 0; e < N; ++e) rt[e] = sqrt_nr(hh[e]);
-    }
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-        // min(r, 1) as ONE v_min_f64.  The reference's min keeps a NaN; minnum drops it (-> 1.0), but 1.0 is outside the fast domain
-        // of asin_small_b (|x| < 0.5), so such a lane raises `rare` and the fallback below recomputes the NaN-keeping min from rt
-        rm[e] = __builtin_fmin(rt[e], 1.0);
-    }
-    if (tpgb::asin_small_b<N>(rm, as)) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) as[e] = asinD(!(rt[e] >= 1.0) ? rt[e] : 1.0);
-    }
+    for (int e = 0; e < N; ++e) hh[e] = s1[e] * s1[e] + X[e].ca * Y[e].ca * (s2[e] * s2[e]);
+    tpgb::asin_sqrt_b<N>(hh, as);                 // asin(min(sqrt(h), 1)): one rare-argument test for the square root, the clamp and the asin
 #pragma unroll
     for (int e = 0; e < N; ++e) d[e] = (2 * Rad) * as[e];      // 2 (R asin) = (2 R) asin bit for bit: doubling is exact (2 R: wave-uniform)
 }
@@ -662,8 +663,10 @@ __device__ __forceinline__ void hav_batch(const Nb (&X)[N], const Nb (&Y)[N], do
 #endif                         // 2 compute-only (values folded, one store per lane), 3 = 2 without the table loads; results are WRONG by design
 #if TPG_CELLS_PROBE == 2 || TPG_CELLS_PROBE == 3
 #define TPG_EMIT(A, OFF, V) (fold ^= (unsigned long long)__double_as_longlong(V) + (A), fold_off = (OFF), folded = true)
+#define TPG_EMIT_PINNED(A, OFF, V) TPG_EMIT(A, OFF, V)
 #else
 #define TPG_EMIT(A, OFF, V) put32<T, NT>(o, A, OFF, V)
+#define TPG_EMIT_PINNED(A, OFF, V) put32<T, NT, false>(o, A, OFF, V)      // OFF left pin_off() in this basic block
 #endif
 
 // XCD-grouped order: a permutation inside every whole group of 64 block ids that gives the ids with one value of id mod 8 -- one XCD's
@@ -725,7 +728,10 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
     // ---- phase 1: one point set per thread
     Step4 q;
     if (active_row) {
-        const bool fast = s >= 1 && s < g.Ny && fast_grid;                   // wave-uniform
+        // wave-uniform (TPG_RARE: always true in the ledger's scratch build).  s >= 0 always; row s = 0 -- the apron wave of the southernmost
+        // tile row of a band that starts at row 1 -- is on the fast path too: its Face-y points FF(1), CF(1) are ordinary row-1 points,
+        // and its Center-y points are the zero south halo, set below (the row table was loaded for the clamped row 1: any finite chain)
+        const bool fast = !TPG_RARE(!(s < g.Ny && fast_grid));
         if (fast) {
             int i0 = i - g.shift; if (i0 < 1) i0 += g.Nx;
             lc.hemi = (i0 <= g.Nx / 2) ? -90.0 : 90.0;
@@ -743,14 +749,14 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
         // coordinates: rows p >= 1 emit CC/FC(s) and FF/CF(s+1); the first tile's apron row emits FF/CF(jm_lo)
         if (col_emit) {
             if (p >= 1 && s >= g.jm_lo) {
-                unsigned off = rowoff(s);
-                TPG_EMIT(TPG_LAMBDA_FC, off, q.lam[0]); TPG_EMIT(TPG_PHI_FC, off, q.phi[0]);
-                TPG_EMIT(TPG_LAMBDA_CC, off, q.lam[1]); TPG_EMIT(TPG_PHI_CC, off, q.phi[1]);
+                const unsigned off = pin_off(rowoff(s));
+                TPG_EMIT_PINNED(TPG_LAMBDA_FC, off, q.lam[0]); TPG_EMIT_PINNED(TPG_PHI_FC, off, q.phi[0]);
+                TPG_EMIT_PINNED(TPG_LAMBDA_CC, off, q.lam[1]); TPG_EMIT_PINNED(TPG_PHI_CC, off, q.phi[1]);
             }
             if ((p >= 1 || ty == 0) && s + 1 >= g.jm_lo && s + 1 <= g.jm_hi) {
-                unsigned off1 = rowoff(s + 1);
-                TPG_EMIT(TPG_LAMBDA_FF, off1, q.lam[2]); TPG_EMIT(TPG_PHI_FF, off1, q.phi[2]);
-                TPG_EMIT(TPG_LAMBDA_CF, off1, q.lam[3]); TPG_EMIT(TPG_PHI_CF, off1, q.phi[3]);
+                const unsigned off1 = pin_off(rowoff(s + 1));
+                TPG_EMIT_PINNED(TPG_LAMBDA_FF, off1, q.lam[2]); TPG_EMIT_PINNED(TPG_PHI_FF, off1, q.phi[2]);
+                TPG_EMIT_PINNED(TPG_LAMBDA_CF, off1, q.lam[3]); TPG_EMIT_PINNED(TPG_PHI_CF, off1, q.phi[3]);
             }
         }
         double (*L)[R][64] = lds.v;
@@ -760,6 +766,15 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
         L[L_FF + 0][p][lane] = q.lam[2]; L[L_FF + 1][p][lane] = q.a[2]; L[L_FF + 2][p][lane] = q.ca[2];
         L[L_FF + 3][p][lane] = q.X[1];   L[L_FF + 4][p][lane] = q.Y[1]; L[L_FF + 5][p][lane] = q.Z[1];
         L[L_CF + 0][p][lane] = q.lam[3]; L[L_CF + 1][p][lane] = q.a[3]; L[L_CF + 2][p][lane] = q.ca[3];
+        if (s == 0 && fast_grid) {
+            // FC(0), CC(0) of the fast path: what coord() yields below row 1 -- (lambda, phi) = (0, 0), so a = 0 deg2rad = 0, cos(0) = 1
+            // and the unit vector (cosd 0 cosd 0, sind 0 cosd 0, sind 0) = (1, +0, +0).  Row 0 is an apron row (p = 0): nothing of it is
+            // emitted and phase 2 reads it from LDS only, so the records are overwritten here (LDS operations of a wave execute in order)
+            // and not in q, where the merge would cost every wave its moves.  tests/test_cells_trims3.py holds them against k_cells.
+            L[L_FC + 0][p][lane] = 0.0; L[L_FC + 1][p][lane] = 0.0; L[L_FC + 2][p][lane] = 1.0;
+            L[L_CC + 0][p][lane] = 0.0; L[L_CC + 1][p][lane] = 0.0; L[L_CC + 2][p][lane] = 1.0;
+            L[L_CC + 3][p][lane] = 1.0; L[L_CC + 4][p][lane] = 0.0; L[L_CC + 5][p][lane] = 0.0;
+        }
     }
     __syncthreads();                                                         // the only barrier: point sets in LDS
     if (p == 0) {
@@ -802,13 +817,21 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
         if (col_emit) {                                                      // nor have apron lanes
         // ---- phase 2: the cell (i, s) from own registers + LDS neighbours, loaded just in time so that the
         //      live set stays under 128 VGPRs (4 waves/SIMD supply the ILP; batches of 2 suffice)
-        double (*L)[R][64] = lds.v;
-        const int pm = p - 1, le = lane + 1, lw = lane - 1;
+        // LDS addresses: one VGPR base per lane shift -- this lane, its east and its west neighbour, all at row p - 1 -- and the plane
+        // f and the row (0: p - 1, 1: p) as the immediate offset of the read, (f R + row) * 512 B.  The bases are opaque to the compiler
+        // (lds_base), so it pairs reads of one base across planes (ds_read2st64_b64, offsets in units of 512 B: any plane and row fits)
+        // and not across lanes (ds_read2_b64 on lane, lane + 1 of one plane: 2040 B of reach, so a v_add_u32 per plane for a new base).
+        // A single read reaches 65535 B: this lane and its west neighbour are read on planes 3 (L_CC) to 17 only, so their bases sit on
+        // plane 2 and the planes 16, 17 need no second base.
+        const int pm = p - 1;
+        const LdsBase b0 = { lds_base(&lds.v[2][pm][lane]), 2 }, bW = { lds_base(&lds.v[2][pm][lane - 1]), 2 };
+        const LdsBase bE = { lds_base(&lds.v[0][pm][lane + 1]), 0 };
+        auto rd = [&](const LdsBase& b, int f, int row) -> double { return b.p[((f - b.plane) * R + row) * 64]; };
         const unsigned off = rowoff(s);
         double d[8];
 #if TPG_CELLS_PROBE == 1
         {
-            const double pv = q.lam[0] + L[L_FC + 0][pm][le];
+            const double pv = q.lam[0] + rd(bE, L_FC + 0, 0);
             TPG_EMIT(TPG_AZ_CC, off, pv); TPG_EMIT(TPG_AZ_FF, off, pv);
 #pragma unroll
             for (int k = 0; k < 8; ++k) d[k] = pv;
@@ -819,20 +842,20 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
         for (int k = 0; k < 2; ++k) {
             V3 a, b, c, dd;
             if (k == 0) {   // ffP = FF(i,s), ffEP = FF(i+1,s), ffE = FF(i+1,s+1), ff = FF(i,s+1)
-                a = V3{ L[L_FF + 3][pm][lane], L[L_FF + 4][pm][lane], L[L_FF + 5][pm][lane] };
-                b = V3{ L[L_FF + 3][pm][le], L[L_FF + 4][pm][le], L[L_FF + 5][pm][le] };
-                c = V3{ L[L_FF + 3][p][le], L[L_FF + 4][p][le], L[L_FF + 5][p][le] };
+                a = V3{ rd(b0, L_FF + 3, 0), rd(b0, L_FF + 4, 0), rd(b0, L_FF + 5, 0) };
+                b = V3{ rd(bE, L_FF + 3, 0), rd(bE, L_FF + 4, 0), rd(bE, L_FF + 5, 0) };
+                c = V3{ rd(bE, L_FF + 3, 1), rd(bE, L_FF + 4, 1), rd(bE, L_FF + 5, 1) };
                 dd = V3{ q.X[1], q.Y[1], q.Z[1] };
             } else {        // ccWP = CC(i-1,s-1), ccP = CC(i,s-1), cc = CC(i,s), ccW = CC(i-1,s)
-                a = V3{ L[L_CC + 3][pm][lw], L[L_CC + 4][pm][lw], L[L_CC + 5][pm][lw] };
-                b = V3{ L[L_CC + 3][pm][lane], L[L_CC + 4][pm][lane], L[L_CC + 5][pm][lane] };
+                a = V3{ rd(bW, L_CC + 3, 0), rd(bW, L_CC + 4, 0), rd(bW, L_CC + 5, 0) };
+                b = V3{ rd(b0, L_CC + 3, 0), rd(b0, L_CC + 4, 0), rd(b0, L_CC + 5, 0) };
                 c = V3{ q.X[0], q.Y[0], q.Z[0] };
-                dd = V3{ L[L_CC + 3][p][lw], L[L_CC + 4][p][lw], L[L_CC + 5][p][lw] };
+                dd = V3{ rd(bW, L_CC + 3, 1), rd(bW, L_CC + 4, 1), rd(bW, L_CC + 5, 1) };
             }
             double tt[4], at[4];
             tt[0] = tri_tan_nr(a, b, c); tt[1] = tri_tan_nr(a, b, dd);
             tt[2] = tri_tan_nr(a, c, dd); tt[3] = tri_tan_nr(b, c, dd);
-            if (__any(tpgb::atan_small_b<4>(tt, at))) {                 // wave-uniform fallback (large or degenerate triangles)
+            if (__any(tpgb::atan_small_b<4, true>(tt, at))) {           // wave-uniform fallback (large, degenerate or negative triangles)
                 tt[0] = tri_tan(a, b, c); tt[1] = tri_tan(a, b, dd); tt[2] = tri_tan(a, c, dd); tt[3] = tri_tan(b, c, dd);
                 tpgb::atan_b<4>(tt, at);
             }
@@ -847,32 +870,33 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
 
         // 8 haversines in pairs; operand e = (x point, y point), each {lam, a, ca}
         //   0 dxcc(fcE,fc) 1 dxfc(cc,ccW) 2 dxcf(ffEP,ffP) 3 dxff(cfP,cfWP) 4 dycc(cf,cfP) 5 dyfc(ff,ffP) 6 dycf(cc,ccP) 7 dyff(fc,fcP)
-        auto ld = [&](int f, int pp, int ll) -> Nb { return Nb{ L[f + 0][pp][ll], L[f + 1][pp][ll], L[f + 2][pp][ll] }; };
+        auto ld = [&](int f, int row, const LdsBase& b) -> Nb { return Nb{ rd(b, f + 0, row), rd(b, f + 1, row), rd(b, f + 2, row) }; };
         const Nb own[4] = { Nb{ q.lam[0], q.a[0], q.ca[0] }, Nb{ q.lam[1], q.a[1], q.ca[1] },
                             Nb{ q.lam[2], q.a[2], q.ca[2] }, Nb{ q.lam[3], q.a[3], q.ca[3] } };   // fc cc ff cf
 #pragma unroll
         for (int hb = 0; hb < 6; hb += 2) {
             Nb X[2], Y[2];
-            if (hb == 0)      { X[0] = ld(L_FC, p, le); Y[0] = own[0];            X[1] = own[1];            Y[1] = ld(L_CC, p, lw); }
-            else if (hb == 2) { X[0] = ld(L_FF, pm, le); Y[0] = ld(L_FF, pm, lane); X[1] = ld(L_CF, pm, lane); Y[1] = ld(L_CF, pm, lw); }
-            else              { X[0] = own[3];           Y[0] = ld(L_CF, pm, lane); X[1] = own[2];            Y[1] = ld(L_FF, pm, lane); }
+            if (hb == 0)      { X[0] = ld(L_FC, 1, bE); Y[0] = own[0];          X[1] = own[1];          Y[1] = ld(L_CC, 1, bW); }
+            else if (hb == 2) { X[0] = ld(L_FF, 0, bE); Y[0] = ld(L_FF, 0, b0); X[1] = ld(L_CF, 0, b0); Y[1] = ld(L_CF, 0, bW); }
+            else              { X[0] = own[3];          Y[0] = ld(L_CF, 0, b0); X[1] = own[2];          Y[1] = ld(L_FF, 0, b0); }
             double dd2[2];
             hav_batch<2>(X, Y, Rad, dd2);
             d[hb] = dd2[0]; d[hb + 1] = dd2[1];
         }
         {   // Dy_cf here; Dy_ff is the apron wave's
-            Nb X[1] = { own[1] }, Y[1] = { ld(L_CC, pm, lane) };
+            Nb X[1] = { own[1] }, Y[1] = { ld(L_CC, 0, b0) };
             double dd1[1];
             hav_batch<1>(X, Y, Rad, dd1);
             d[6] = dd1[0];
         }
 #endif
-        TPG_EMIT(TPG_DX_CC, off, d[0]); TPG_EMIT(TPG_DX_FC, off, d[1]);
-        TPG_EMIT(TPG_DX_CF, off, d[2]); TPG_EMIT(TPG_DX_FF, off, d[3]);
-        TPG_EMIT(TPG_DY_CC, off, d[4]); TPG_EMIT(TPG_DY_FC, off, d[5]);
-        TPG_EMIT(TPG_DY_CF, off, d[6]);
-        TPG_EMIT(TPG_AZ_FC, off, d[5] * d[1]);
-        TPG_EMIT(TPG_AZ_CF, off, d[6] * d[2]);
+        const unsigned offe = pin_off(off);                                  // the nine stores below are one basic block
+        TPG_EMIT_PINNED(TPG_DX_CC, offe, d[0]); TPG_EMIT_PINNED(TPG_DX_FC, offe, d[1]);
+        TPG_EMIT_PINNED(TPG_DX_CF, offe, d[2]); TPG_EMIT_PINNED(TPG_DX_FF, offe, d[3]);
+        TPG_EMIT_PINNED(TPG_DY_CC, offe, d[4]); TPG_EMIT_PINNED(TPG_DY_FC, offe, d[5]);
+        TPG_EMIT_PINNED(TPG_DY_CF, offe, d[6]);
+        TPG_EMIT_PINNED(TPG_AZ_FC, offe, d[5] * d[1]);
+        TPG_EMIT_PINNED(TPG_AZ_CF, offe, d[6] * d[2]);
         }
     }
 #if TPG_CELLS_PROBE == 2 || TPG_CELLS_PROBE == 3
@@ -880,6 +904,7 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
 #endif
 }
 #undef TPG_EMIT
+#undef TPG_EMIT_PINNED
 
 // ---- K2: halo cells of the 20 arrays ------------------------------------------------------------
 // x/y location of array q (order of enum tpg_array)
