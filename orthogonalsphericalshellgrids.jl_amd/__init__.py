@@ -35,5 +35,7 @@ from .free_surface import (SplitExplicitFreeSurface, SplitExplicitSubcyclePlan, 
 from .time_stepping import (Ab2StepPlan, Ab2VelocityStepPlan, ab2_step_fields, ab2_step_plan, ab2_step_velocities, ab2_velocity_step_plan)
 from .advection import TracerAdvectionPlan, tracer_advection_plan, tracer_advection_tendency
 from .momentum import MomentumAdvectionPlan, momentum_advection_plan, momentum_advection_tendency
+from .weno import (WENO, Centered, FluxFormAdvection, WenoTracerAdvectionPlan, weno_tracer_advection_plan,
+                   weno_tracer_advection_tendency)
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]
