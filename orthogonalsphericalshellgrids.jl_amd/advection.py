@@ -39,21 +39,20 @@ def _same(a, b):
     return a is b or a.data is b.data or a.data.data_ptr() == b.data.data_ptr()
 
 
-class TracerAdvectionPlan(OperatorPlan):
-    """tracer_advection_tendency(tracers, u, v, w, out=G) with the arguments built once: `plan()` issues ONE tpg_tracer_advection_tendency
-    call per 16 tracers on torch's current stream and then, with `fill_halos`, ONE HaloFillPlan of those G that have conditions.  It
-    allocates nothing when called and is a single chain of launches, so it replays inside torch.cuda.graph.  On an ImmersedBoundaryGrid with
-    `mask_immersed` the (Center, Center) count plane and the value 0 go into the call.  The plan holds the tensors of the tracers, u, v, w and
-    G, the metric arrays, the spacings and the count plane: rebuild it if a field's `data` is replaced."""
+class _TracerTendencyPlan(OperatorPlan):
+    """The plan of a flux-form tracer tendency, whatever the scheme: the checks of the fields, the metric arrays, one C call per 16 tracers and
+    the halo fill of those G that have conditions.  A scheme's class (TracerAdvectionPlan here, WenoTracerAdvectionPlan in weno.py) supplies
+    what differs: `_refuse(scheme, what)`, the smallest halo `_HALO` with the sentence `_HALO_RULE` of its refusal, the band refusal's
+    `_BAND_ROWS`, `_LIBRARY` (the names in _lib of the loader and the checker, and the C function) and `_extra(scheme)`, the arguments
+    between the mask value and Nx."""
 
-    def __init__(self, tracers, u, v, w, G, *, scheme="centered2", mask_immersed=True, fill_halos=False, what="tracer_advection_plan"):
+    def __init__(self, tracers, u, v, w, G, *, scheme, mask_immersed, fill_halos, what):
         tracers, G = list(tracers), list(G)
         if not tracers:
             raise TypeError(f"{what}: no tracers")
         if len(tracers) != len(G):
             raise TypeError(f"{what}: tracers and G are lists of one length ({len(tracers)}, {len(G)})")
-        if scheme not in _SCHEMES:
-            raise NotImplementedError(f"{what}: advection scheme {scheme!r} is not built ('centered2' is; upwind and WENO are not)")
+        self._refuse(scheme, what)
         names = {"u": (u, _LOCS["u"]), "v": (v, _LOCS["v"]), "w": (w, _LOCS["w"])}
         for q, (c, g) in enumerate(zip(tracers, G)):
             names.update({f"tracer {q}": (c, _LOCS["c"]), f"G of tracer {q}": (g, _LOCS["c"])})
@@ -65,23 +64,23 @@ class TracerAdvectionPlan(OperatorPlan):
             for p in range(q):
                 if _same(g, G[p]):
                     raise ValueError(f"{what}: G of tracer {q} and G of tracer {p} are one field")
-        if min(first.Hx, first.Hy, first.Hz) < 1:
-            raise ValueError(f"{what}: the rule reads one cell beyond the interior on every side: every halo must be at least 1 "
-                             f"(halo ({first.Hx}, {first.Hy}, {first.Hz}))")
+        if any(h < least for h, least in zip((first.Hx, first.Hy, first.Hz), self._HALO)):
+            raise ValueError(f"{what}: {self._HALO_RULE} (halo ({first.Hx}, {first.Hy}, {first.Hz}))")
         g = _bare(first.grid)
         if g.global_size and g.Ny != g.global_size[1]:
-            raise NotImplementedError(f"{what}: latitude-band grids are not handled: the row Ny + 1 of a band is the exchanged halo row, and "
-                                      "the band path of the tracer tendency is not tested yet")
+            raise NotImplementedError(f"{what}: latitude-band grids are not handled: {self._BAND_ROWS}, and the band path of the tracer "
+                                      "tendency is not tested yet")
         self.tracers, self.u, self.v, self.w, self.G, self.scheme = tracers, u, v, w, G, scheme
         dtype, device = u.data.dtype, u.data.device
-        lib = _lib.advection_lib()
+        load, check, function = self._LIBRARY
+        function, check = getattr(getattr(_lib, load)(), function), getattr(_lib, check)
         counts = getattr(first.grid, "column_counts", None) if mask_immersed else None
         ncc = None if counts is None else counts["cc"]
         with _on_device(device):
             dy, dx, az = (_metric(g, name, dtype, device) for name in ("dy_fc", "dx_cf", "az_cc"))
             dz = _grid_table(g, "_z_center_spacings", z_center_spacings, dtype, device)
         shared = [u.data, v.data, w.data, dy, dx, az, dz, ncc]
-        tail = (*(_ptr(t) for t in shared), 0.0, _SCHEMES[scheme], u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
+        tail = (*(_ptr(t) for t in shared), 0.0, *self._extra(scheme), u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
         calls = []
         for f0 in range(0, len(tracers), _lib.TPG_MAX_FIELDS):     # more than 16 tracers go in several calls, as the AB2 step's do
             sl = slice(f0, f0 + _lib.TPG_MAX_FIELDS)
@@ -91,10 +90,43 @@ class TracerAdvectionPlan(OperatorPlan):
         before = []
         for _, args in calls[:-1]:
             p = OperatorPlan()
-            p._set_call(lib.tpg_tracer_advection_tendency, args, _lib.check_advection, device, held)
+            p._set_call(function, args, check, device, held)
             before.append(p)
-        self._set_call(lib.tpg_tracer_advection_tendency, calls[-1][1], _lib.check_advection, device, held, G if fill_halos else (),
-                       before=before)
+        self._set_call(function, calls[-1][1], check, device, held, G if fill_halos else (), before=before)
+
+
+def _tendency_fields(tracers, out, what):
+    """the `out` of a one-shot call: as given, or a new Field at (Center, Center, Center) per tracer"""
+    if out is not None:
+        return out
+    for q, c in enumerate(tracers):
+        if not isinstance(c, Field) or c.loc != _LOCS["c"]:
+            raise TypeError(f"{what}: tracer {q} must be a Field at (Center, Center, Center)")
+    return [Field(_LOCS["c"], c.grid, name="G") for c in tracers]
+
+
+class TracerAdvectionPlan(_TracerTendencyPlan):
+    """tracer_advection_tendency(tracers, u, v, w, out=G) with the arguments built once: `plan()` issues ONE tpg_tracer_advection_tendency
+    call per 16 tracers on torch's current stream and then, with `fill_halos`, ONE HaloFillPlan of those G that have conditions.  It
+    allocates nothing when called and is a single chain of launches, so it replays inside torch.cuda.graph.  On an ImmersedBoundaryGrid with
+    `mask_immersed` the (Center, Center) count plane and the value 0 go into the call.  The plan holds the tensors of the tracers, u, v, w and
+    G, the metric arrays, the spacings and the count plane: rebuild it if a field's `data` is replaced."""
+    _HALO = (1, 1, 1)
+    _HALO_RULE = "the rule reads one cell beyond the interior on every side: every halo must be at least 1"
+    _BAND_ROWS = "the row Ny + 1 of a band is the exchanged halo row"
+    _LIBRARY = ("advection_lib", "check_advection", "tpg_tracer_advection_tendency")
+
+    def __init__(self, tracers, u, v, w, G, *, scheme="centered2", mask_immersed=True, fill_halos=False, what="tracer_advection_plan"):
+        super().__init__(tracers, u, v, w, G, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos, what=what)
+
+    @staticmethod
+    def _refuse(scheme, what):
+        if scheme not in _SCHEMES:
+            raise NotImplementedError(f"{what}: advection scheme {scheme!r} is not built ('centered2' is; upwind and WENO are not)")
+
+    @staticmethod
+    def _extra(scheme):
+        return (_SCHEMES[scheme],)
 
 
 def tracer_advection_plan(tracers, u, v, w, G, *, scheme="centered2", mask_immersed=True, fill_halos=False):
@@ -110,11 +142,7 @@ def tracer_advection_tendency(tracers, u, v, w, out=None, *, scheme="centered2",
     nodes under the bottom get 0.  Only the interior of each G is written; `fill_halos` then fills those that have conditions.  Returns the
     list.  Builds a TracerAdvectionPlan and runs it once; use tracer_advection_plan in a time loop."""
     tracers = list(tracers)
-    if out is None:
-        for q, c in enumerate(tracers):
-            if not isinstance(c, Field) or c.loc != _LOCS["c"]:
-                raise TypeError(f"tracer_advection_tendency: tracer {q} must be a Field at (Center, Center, Center)")
-        out = [Field(_LOCS["c"], c.grid, name="G") for c in tracers]
+    out = _tendency_fields(tracers, out, "tracer_advection_tendency")
     plan = TracerAdvectionPlan(tracers, u, v, w, out, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos,
                                what="tracer_advection_tendency")
     plan()

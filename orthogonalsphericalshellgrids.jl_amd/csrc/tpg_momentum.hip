@@ -328,9 +328,6 @@ __global__ __launch_bounds__(256, WAVES) void k_momentum_advection(MomPtrs p, Mo
     }
 }
 
-// an array of the call: where it is, how long, what the messages call it
-struct Span { const void* p; unsigned long long bytes; const char* name; };
-
 }  // namespace
 
 extern "C" {

@@ -1,6 +1,8 @@
 // tpg_operator.hpp -- what the operator translation units share (tpg_operators.hip, tpg_continuity.hip, tpg_barotropic.hip,
-// tpg_free_surface.hip; each is a library of its own): the chunk and count access types and the store of their kernels, and the arithmetic
-// their entry points check arguments with.  An entry point keeps its own sequence of checks, statuses and messages; a new operator starts here.
+// tpg_free_surface.hip, tpg_timestep.hip, tpg_momentum.hip and, through tpg_tracer_tendency.hpp, tpg_advection.hip and tpg_weno.hip; each is
+// a library of its own): the chunk and count access types and the store of their kernels, and the arithmetic, the Span record and the overlap
+// check their entry points check arguments with.  An entry point keeps its own sequence of checks, statuses and messages; a new operator
+// starts here.
 #pragma once
 #include "tpg_launch.hpp"
 
@@ -34,6 +36,24 @@ bool arrays_overlap(const void* p, unsigned long long pbytes, const void* q, uns
 {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
     return a < b ? b - a < pbytes : a - b < qbytes;
+}
+
+// an array of a call: where it is, how long, what the messages call it, whether the call writes it
+struct Span { const void* p; unsigned long long bytes; char name[24]; bool written; };
+
+// any written array against every other array of the call.  A call whose messages or order differ keeps its own loop (the tracer tendencies,
+// tpg_tracer_tendency.hpp; tpg_momentum.hip)
+int check_overlaps(const Span* s, int n, const char* why)
+{
+    for (int o = 0; o < n; ++o) {
+        if (!s[o].p || !s[o].written) continue;
+        for (int q = 0; q < n; ++q)
+            if (q != o && s[q].p && arrays_overlap(s[o].p, s[o].bytes, s[q].p, s[q].bytes)) {
+                tpg::set_error("%s overlaps %s (%s)", s[o].name, s[q].name, why);
+                return TPG_ERR_INVALID_ARGUMENT;
+            }
+    }
+    return TPG_OK;
 }
 
 // the first interior cell of a padded plane (sx * Hy + Hx) and of a 3-D parent (plane * Hz + that)

@@ -216,23 +216,6 @@ int check_shape(int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int Hy2, int ft,
     return TPG_OK;
 }
 
-// an array of a call: where it is, how long, what the messages call it, whether the call writes it
-struct Span { const void* p; unsigned long long bytes; char name[24]; bool written; };
-
-// any written array against every other array of the call
-int check_overlaps(const Span* s, int n, const char* why)
-{
-    for (int o = 0; o < n; ++o) {
-        if (!s[o].p || !s[o].written) continue;
-        for (int q = 0; q < n; ++q)
-            if (q != o && s[q].p && arrays_overlap(s[o].p, s[o].bytes, s[q].p, s[q].bytes)) {
-                tpg::set_error("%s overlaps %s (%s)", s[o].name, s[q].name, why);
-                return TPG_ERR_INVALID_ARGUMENT;
-            }
-    }
-    return TPG_OK;
-}
-
 // T values in doubles: c1 = T(1.5) + chi_T, c2 = T(0.5) + chi_T, dt_T
 template <typename T>
 void ab2_constants(Ab2Args& a, double dt, double chi)

@@ -37,6 +37,7 @@
 // 16-B chunks where rows and pointers sit on the 16-B grid, the same chunks element-aligned otherwise: chunk_plan's plain / GEN split over
 // all the arrays passed.  Element offsets are 64-bit.  No atomics, no LDS, nothing allocated, no host wait.
 #include "tpg_operator.hpp"
+#include "tpg_tracer_tendency.hpp"
 #include "../../include/tripolar_hip_weno.h"
 
 // compile-time switches of the A/B in profiles/weno/ (make WENO_TAG=_jt1 WENO_FLAGS=-DTPG_WENO_JT=1, -DTPG_WENO_SHARE=0, -DTPG_WENO_TG=2,
@@ -350,9 +351,6 @@ __global__ __launch_bounds__(256, WAVES) void k_weno_tracer_advection(WenoPtrs p
     }
 }
 
-// an array of the call: where it is, how long, what the messages call it
-struct Span { const void* p; unsigned long long bytes; char name[16]; };
-
 }  // namespace
 
 extern "C" {
@@ -365,70 +363,15 @@ int tpg_weno_tracer_advection_tendency(const void* const* c, void* const* G, int
                                        double mask_value, int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
     if (int rc = tpg::check_geom(Nx, Ny, Nz, Hx, Hy, Hz, ft)) return rc;
-    if (nfields < 1) { tpg::set_error("no tracers (nfields = %d)", nfields); return TPG_ERR_INVALID_ARGUMENT; }
-    if (nfields > TPG_MAX_FIELDS) { tpg::set_error("%d tracers: at most TPG_MAX_FIELDS = %d in one call", nfields, TPG_MAX_FIELDS); return TPG_ERR_INVALID_ARGUMENT; }
-    if (!c || !G) { tpg::set_error("null table of tracers or of tendencies"); return TPG_ERR_INVALID_ARGUMENT; }
-    for (int q = 0; q < nfields; ++q) {
-        if (!c[q]) { tpg::set_error("null tracer %d", q); return TPG_ERR_INVALID_ARGUMENT; }
-        if (!G[q]) { tpg::set_error("null G of tracer %d", q); return TPG_ERR_INVALID_ARGUMENT; }
-    }
-    if (!u || !v || !w) { tpg::set_error("null u, v or w"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (!dy_fc || !dx_cf || !az_cc || !dz_c) { tpg::set_error("null dy_fc, dx_cf, az_cc or dz_c"); return TPG_ERR_INVALID_ARGUMENT; }
-    const size_t esz = elem_size(ft);
-    const Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
-    const unsigned long long bytes = (unsigned long long)g.plane * (Nz + 2 * Hz) * esz;            // c, G, u, v
-    const unsigned long long wbytes = (unsigned long long)g.plane * (Nz + 1 + 2 * Hz) * esz;       // w: one more level
-    Span in[TPG_MAX_FIELDS + 3], out[TPG_MAX_FIELDS];
-    for (int q = 0; q < nfields; ++q) {
-        in[q] = Span{ c[q], bytes, "" };
-        out[q] = Span{ G[q], bytes, "" };
-        snprintf(in[q].name, sizeof in[q].name, "tracer %d", q);
-        snprintf(out[q].name, sizeof out[q].name, "G of tracer %d", q);
-    }
-    in[nfields] = Span{ u, bytes, "u" };
-    in[nfields + 1] = Span{ v, bytes, "v" };
-    in[nfields + 2] = Span{ w, wbytes, "w" };
-    for (int q = 0; q < nfields; ++q)
-        if (misaligned(esz, in[q].p)) { tpg::set_error("%s: pointer not aligned to its element type", in[q].name); return TPG_ERR_INVALID_ARGUMENT; }
-    for (int q = 0; q < nfields; ++q)
-        if (misaligned(esz, out[q].p)) { tpg::set_error("%s: pointer not aligned to its element type", out[q].name); return TPG_ERR_INVALID_ARGUMENT; }
-    if (misaligned(esz, u, v, w)) { tpg::set_error("u, v or w pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (misaligned(esz, dy_fc, dx_cf, az_cc, dz_c)) {
-        tpg::set_error("dy_fc, dx_cf, az_cc or dz_c pointer not aligned to its element type");
-        return TPG_ERR_INVALID_ARGUMENT;
-    }
-    if ((uintptr_t)n_cc % 4) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }
-    for (int q = 0; q < nfields; ++q) {
-        for (int s = 0; s < nfields + 3; ++s)
-            if (arrays_overlap(out[q].p, out[q].bytes, in[s].p, in[s].bytes)) {
-                tpg::set_error("%s overlaps %s (every item reads cells while its neighbours write)", out[q].name, in[s].name);
-                return TPG_ERR_INVALID_ARGUMENT;
-            }
-        for (int s = 0; s < q; ++s)
-            if (arrays_overlap(out[q].p, out[q].bytes, out[s].p, out[s].bytes)) {
-                tpg::set_error("%s overlaps %s", out[q].name, out[s].name);
-                return TPG_ERR_INVALID_ARGUMENT;
-            }
-    }
-    if (Hx < HALO || Hy < HALO || Hz < 1) {
-        tpg::set_error("the rule reads c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-1..k+1], u[i+1, j] and v[i, j+1]: Hx >= 3, Hy >= 3 and Hz >= 1 needed "
-                       "(halo (%d,%d,%d))", Hx, Hy, Hz);
-        return TPG_ERR_UNSUPPORTED;
-    }
+    const TracerCall call{ c, G, nfields, u, v, w, dy_fc, dx_cf, az_cc, dz_c, n_cc, tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz), ft };
+    if (int rc = call.check(HALO, 1, "c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-1..k+1]")) return rc;
+    const Geom& g = call.g;
     const long long tiles = (Ny + JT - 1) / JT;
     const long long widest = (long long)(Nx / 2 + CHUNKS_PER_WAVE - 1) / CHUNKS_PER_WAVE * LANES;      // threads per row tile, at most: the SHARE form with W = 2
     if (tiles * widest >= (1ll << 31) - 256) { tpg::set_error("tracer advection: too many work items for 32-bit indexing"); return TPG_ERR_UNSUPPORTED; }
-    WenoPtrs p{};
+    const WenoPtrs p = call.pointers<WenoPtrs>();
     void* arrays[2 * TPG_MAX_FIELDS + 6];
-    int na = 0;
-    for (int q = 0; q < nfields; ++q) {
-        p.c[q] = c[q];
-        p.G[q] = G[q];
-        arrays[na++] = const_cast<void*>(c[q]);
-        arrays[na++] = G[q];
-    }
-    p.u = u; p.v = v; p.w = w; p.dy = dy_fc; p.dx = dx_cf; p.az = az_cc; p.dz = dz_c; p.ncc = n_cc;
-    for (const void* x : { u, v, w, dy_fc, dx_cf, az_cc }) arrays[na++] = const_cast<void*>(x);
+    const int na = call.arrays(arrays);
     hipStream_t st = tpg::as_stream(stream);
     return dispatch_ft(ft, [&](auto ty) {
         typedef decltype(ty) T;
@@ -445,15 +388,10 @@ int tpg_weno_tracer_advection_tendency(const void* const* c, void* const* G, int
             auto launch = [&](auto mask, auto sh) {
                 constexpr bool MASK = decltype(mask)::value;
                 constexpr bool SHARE = decltype(sh)::value;
-                auto groups_of = [&](auto tg) {                    // the whole groups of TG among the tracers not yet taken
-                    constexpr int TG = decltype(tg)::value;
-                    const int n = (nfields - a.q0) / TG;
-                    if (n) hipLaunchKernelGGL((k_weno_tracer_advection<T, W, GEN, MASK, TG, LOOKAHEAD, SHARE>), dim3(blocks, n), dim3(256), 0, st, p, a);
-                    a.q0 += n * TG;
-                };
-                if constexpr (GROUP >= 4) groups_of(std::integral_constant<int, 4>{});
-                if constexpr (GROUP >= 2) groups_of(std::integral_constant<int, 2>{});
-                groups_of(std::integral_constant<int, 1>{});
+                tracer_groups<GROUP>(nfields, [&](auto tg, int q0, int n) {
+                    a.q0 = q0;
+                    hipLaunchKernelGGL((k_weno_tracer_advection<T, W, GEN, MASK, decltype(tg)::value, LOOKAHEAD, SHARE>), dim3(blocks, n), dim3(256), 0, st, p, a);
+                });
             };
             auto by_mask = [&](auto sh) {
                 if (n_cc) launch(std::true_type{}, sh);

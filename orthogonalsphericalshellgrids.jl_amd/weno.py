@@ -20,12 +20,7 @@ stretched-grid coefficients; WENO in z; other orders; WENOVectorInvariant for th
 The plan form holds its tensors: calling it enqueues on torch's current stream and allocates nothing (usable inside torch.cuda.graph)."""
 from dataclasses import dataclass
 
-from . import _lib
-from ._operator_plan import OperatorPlan, _check_fields, _ptr
-from .advection import _LOCS, _same
-from .fields import Field
-from .reductions import _bare, _grid_table, _metric, z_center_spacings
-from .time_stepping import _on_device
+from .advection import _TracerTendencyPlan, _tendency_fields
 
 
 @dataclass(frozen=True)
@@ -52,63 +47,29 @@ BUILT = FluxFormAdvection(WENO(order=5), WENO(order=5), Centered())
 _BUILT_NAME = "FluxFormAdvection(WENO(order=5), WENO(order=5), Centered())"
 
 
-class WenoTracerAdvectionPlan(OperatorPlan):
+class WenoTracerAdvectionPlan(_TracerTendencyPlan):
     """weno_tracer_advection_tendency(tracers, u, v, w, out=G) with the arguments built once: `plan()` issues ONE
     tpg_weno_tracer_advection_tendency call per 16 tracers on torch's current stream and then, with `fill_halos`, ONE HaloFillPlan of those
     G that have conditions.  It allocates nothing when called and is a single chain of launches, so it replays inside torch.cuda.graph.  On
     an ImmersedBoundaryGrid with `mask_immersed` the (Center, Center) count plane and the value 0 go into the call.  The plan holds the
     tensors of the tracers, u, v, w and G, the metric arrays, the spacings and the count plane: rebuild it if a field's `data` is replaced."""
+    _HALO = (3, 3, 1)
+    _HALO_RULE = "the rule reads three cells beyond the interior in x and y and one in z: the halo must be at least (3, 3, 1)"
+    _BAND_ROWS = "the rows Ny + 1 .. Ny + 3 of a band are exchanged halo rows"
+    _LIBRARY = ("weno_lib", "check_weno", "tpg_weno_tracer_advection_tendency")
 
     def __init__(self, tracers, u, v, w, G, *, scheme=BUILT, mask_immersed=True, fill_halos=False, what="weno_tracer_advection_plan"):
-        tracers, G = list(tracers), list(G)
-        if not tracers:
-            raise TypeError(f"{what}: no tracers")
-        if len(tracers) != len(G):
-            raise TypeError(f"{what}: tracers and G are lists of one length ({len(tracers)}, {len(G)})")
+        super().__init__(tracers, u, v, w, G, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos, what=what)
+
+    @staticmethod
+    def _refuse(scheme, what):
         if not isinstance(scheme, FluxFormAdvection) or scheme != BUILT:
             raise NotImplementedError(f"{what}: advection scheme {scheme!r} is not built ({_BUILT_NAME} is: WENO of order 5 in x and y, "
                                       "Centered() in z)")
-        names = {"u": (u, _LOCS["u"]), "v": (v, _LOCS["v"]), "w": (w, _LOCS["w"])}
-        for q, (c, g) in enumerate(zip(tracers, G)):
-            names.update({f"tracer {q}": (c, _LOCS["c"]), f"G of tracer {q}": (g, _LOCS["c"])})
-        first = _check_fields(names, what, "the tracers, their tendencies, u, v and w")
-        for q, g in enumerate(G):
-            for p, c in enumerate(tracers):
-                if _same(g, c):
-                    raise ValueError(f"{what}: G of tracer {q} is tracer {p} itself (every node reads its neighbours while they are written)")
-            for p in range(q):
-                if _same(g, G[p]):
-                    raise ValueError(f"{what}: G of tracer {q} and G of tracer {p} are one field")
-        if first.Hx < 3 or first.Hy < 3 or first.Hz < 1:
-            raise ValueError(f"{what}: the rule reads three cells beyond the interior in x and y and one in z: the halo must be at least "
-                             f"(3, 3, 1) (halo ({first.Hx}, {first.Hy}, {first.Hz}))")
-        g = _bare(first.grid)
-        if g.global_size and g.Ny != g.global_size[1]:
-            raise NotImplementedError(f"{what}: latitude-band grids are not handled: the rows Ny + 1 .. Ny + 3 of a band are exchanged halo "
-                                      "rows, and the band path of the tracer tendency is not tested yet")
-        self.tracers, self.u, self.v, self.w, self.G, self.scheme = tracers, u, v, w, G, scheme
-        dtype, device = u.data.dtype, u.data.device
-        lib = _lib.weno_lib()
-        counts = getattr(first.grid, "column_counts", None) if mask_immersed else None
-        ncc = None if counts is None else counts["cc"]
-        with _on_device(device):
-            dy, dx, az = (_metric(g, name, dtype, device) for name in ("dy_fc", "dx_cf", "az_cc"))
-            dz = _grid_table(g, "_z_center_spacings", z_center_spacings, dtype, device)
-        shared = [u.data, v.data, w.data, dy, dx, az, dz, ncc]
-        tail = (*(_ptr(t) for t in shared), 0.0, u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
-        calls = []
-        for f0 in range(0, len(tracers), _lib.TPG_MAX_FIELDS):     # more than 16 tracers go in several calls, as the AB2 step's do
-            sl = slice(f0, f0 + _lib.TPG_MAX_FIELDS)
-            tables = [_lib.ptr_table([t.data for t in tracers[sl]]), _lib.ptr_table([t.data for t in G[sl]])]
-            calls.append((tables, (*tables, len(tracers[sl]), *tail)))
-        held = [t.data for t in (*tracers, *G)] + shared + [c[0] for c in calls]
-        before = []
-        for _, args in calls[:-1]:
-            p = OperatorPlan()
-            p._set_call(lib.tpg_weno_tracer_advection_tendency, args, _lib.check_weno, device, held)
-            before.append(p)
-        self._set_call(lib.tpg_weno_tracer_advection_tendency, calls[-1][1], _lib.check_weno, device, held, G if fill_halos else (),
-                       before=before)
+
+    @staticmethod
+    def _extra(scheme):
+        return ()
 
 
 def weno_tracer_advection_plan(tracers, u, v, w, G, *, scheme=BUILT, mask_immersed=True, fill_halos=False):
@@ -125,11 +86,7 @@ def weno_tracer_advection_tendency(tracers, u, v, w, out=None, *, scheme=BUILT, 
     interior of each G is written; `fill_halos` then fills those that have conditions.  Returns the list.  Builds a
     WenoTracerAdvectionPlan and runs it once; use weno_tracer_advection_plan in a time loop."""
     tracers = list(tracers)
-    if out is None:
-        for q, c in enumerate(tracers):
-            if not isinstance(c, Field) or c.loc != _LOCS["c"]:
-                raise TypeError(f"weno_tracer_advection_tendency: tracer {q} must be a Field at (Center, Center, Center)")
-        out = [Field(_LOCS["c"], c.grid, name="G") for c in tracers]
+    out = _tendency_fields(tracers, out, "weno_tracer_advection_tendency")
     plan = WenoTracerAdvectionPlan(tracers, u, v, w, out, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos,
                                    what="weno_tracer_advection_tendency")
     plan()
