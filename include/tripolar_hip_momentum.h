@@ -22,7 +22,8 @@ const char *tpg_momentum_last_error(void);
 
 /* `scheme` of tpg_momentum_advection_tendency.  VectorInvariant()'s default is the only one built: the enstrophy-conserving vorticity term,
  * the energy-conserving vertical term and the kinetic-energy gradient.  Every other value is refused with TPG_ERR_UNSUPPORTED, the message
- * names it (the energy-conserving and WENO vector-invariant schemes come later without an ABI change). */
+ * names it (the WENO5-upwinded vorticity term is a call of its own, include/tripolar_hip_weno_momentum.h; the energy-conserving scheme comes
+ * later without an ABI change). */
 #define TPG_MOMENTUM_ENSTROPHY_CONSERVING 0
 
 /* ---- the velocity tendencies a hydrostatic model's AB2 step consumes ----------------------------------------------------------------------

@@ -72,7 +72,7 @@ const char *tpg_weno_last_error(void);
  *   the results are bit-identical however the tracers are grouped.
  * - Stays out.  Oceananigans' drop of the reconstruction order beside the south wall and beside immersed nodes (in both drivers every
  *   row south of -78 degrees and both pole boxes are under the mask, so the rows this touches are masked in the workloads here);
- *   stretched-grid coefficients; WENO in z; other orders; WENOVectorInvariant for the momentum; latitude bands; the Julia hooks.
+ *   stretched-grid coefficients; WENO in z; other orders; latitude bands; the Julia hooks (the momentum half: include/tripolar_hip_weno_momentum.h).
  *
  * Arrays
  * - c[q], G[q], u at (Face, Center, Center) and v at (Center, Face, Center): padded parents of ONE geometry (Nx, Ny, Nz, Hx, Hy, Hz).

@@ -37,5 +37,7 @@ from .advection import TracerAdvectionPlan, tracer_advection_plan, tracer_advect
 from .momentum import MomentumAdvectionPlan, momentum_advection_plan, momentum_advection_tendency
 from .weno import (WENO, Centered, FluxFormAdvection, WenoTracerAdvectionPlan, weno_tracer_advection_plan,
                    weno_tracer_advection_tendency)
+from .weno_momentum import (DefaultStencil, EnergyConserving, EnstrophyConserving, VectorInvariant, VelocityStencil, WenoMomentumAdvectionPlan,
+                            WENOVectorInvariant, weno_momentum_advection_plan, weno_momentum_advection_tendency)
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

@@ -1,13 +1,13 @@
 """ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
 (include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency libraries (_advection.h,
-_momentum.h, _weno.h).
+_momentum.h, _weno.h, _weno_momentum.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
 status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep,
-advection, momentum and weno.
+advection, momentum, weno and weno_momentum.
 """
 import ctypes as C
 import os
@@ -171,6 +171,13 @@ WENO_SIGNATURES = {
     "tpg_weno_tracer_advection_tendency": (_i, [C.POINTER(_vp)] * 2 + [_i] + [_vp] * 8 + [C.c_double] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_weno_momentum.h declares (libtripolar_hip_weno_momentum.so: the tenth library, no test build)
+WENO_MOMENTUM_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno_momentum.so")
+WENO_MOMENTUM_SIGNATURES = {
+    "tpg_weno_momentum_last_error": (C.c_char_p, []),
+    "tpg_weno_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
+}
+
 
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
@@ -221,6 +228,9 @@ OPERATOR_LIBRARIES = (operators_lib, continuity_lib, barotropic_lib, free_surfac
 momentum_lib, check_momentum = _library("_momentum", "MOMENTUM_LIB_PATH", MOMENTUM_SIGNATURES, "tpg_momentum_last_error")
 weno_lib, check_weno = _library("_weno", "WENO_LIB_PATH", WENO_SIGNATURES, "tpg_weno_last_error")
 TENDENCY_LIBRARIES = (advection_lib, momentum_lib, weno_lib)             # what produces the tendencies the AB2 step consumes
+weno_momentum_lib, check_weno_momentum = _library("_weno_momentum", "WENO_MOMENTUM_LIB_PATH", WENO_MOMENTUM_SIGNATURES,
+                                                  "tpg_weno_momentum_last_error")
+MOMENTUM_TENDENCY_LIBRARIES = (momentum_lib, weno_momentum_lib)          # the two vorticity schemes of the velocity tendencies
 
 
 def ft_of(dtype):

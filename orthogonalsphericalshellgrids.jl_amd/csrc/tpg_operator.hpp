@@ -1,5 +1,5 @@
 // tpg_operator.hpp -- what the operator translation units share (tpg_operators.hip, tpg_continuity.hip, tpg_barotropic.hip,
-// tpg_free_surface.hip, tpg_timestep.hip, tpg_momentum.hip and, through tpg_tracer_tendency.hpp, tpg_advection.hip and tpg_weno.hip; each is
+// tpg_free_surface.hip, tpg_timestep.hip, tpg_momentum.hip, tpg_weno_momentum.hip and, through tpg_tracer_tendency.hpp, tpg_advection.hip and tpg_weno.hip; each is
 // a library of its own): the chunk and count access types and the store of their kernels, and the arithmetic, the Span record and the overlap
 // check their entry points check arguments with.  An entry point keeps its own sequence of checks, statuses and messages; a new operator
 // starts here.

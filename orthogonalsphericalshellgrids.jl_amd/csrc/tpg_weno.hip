@@ -4,7 +4,7 @@
 // [recalled: Oceananigans' FluxFormAdvection(WENO(order = 5), WENO(order = 5), Centered()), uniform-grid coefficients, Jiang-Shu smoothness
 // indicators, WENO-Z weights, eps = 1e-8; parity unpinned, like every operator here]
 //
-// THE RULE is written out once, in include/tripolar_hip_weno.h: R(q0..q4) (weno_face below, operation for operation), the selection
+// THE RULE is written out once, in include/tripolar_hip_weno.h: R(q0..q4) (weno_face of tpg_weno_face.hpp, operation for operation), the selection
 // Mx >= 0 ? R(c[i-3..i+1]) : R(c[i+2..i-2]) (upwind_flux below: five selects, ONE evaluation of R per face), Mx, My, Mz, V, Fz and the last
 // line those of tpg_tracer_advection_tendency.  Evaluated in the field type T, in exactly that order, with no contraction; every operation
 // is one correctly rounded IEEE operation.  Each flux is formed once; where one is formed twice (tile edges) it has the same bits.
@@ -38,6 +38,7 @@
 // all the arrays passed.  Element offsets are 64-bit.  No atomics, no LDS, nothing allocated, no host wait.
 #include "tpg_operator.hpp"
 #include "tpg_tracer_tendency.hpp"
+#include "tpg_weno_face.hpp"
 #include "../../include/tripolar_hip_weno.h"
 
 // compile-time switches of the A/B in profiles/weno/ (make WENO_TAG=_jt1 WENO_FLAGS=-DTPG_WENO_JT=1, -DTPG_WENO_SHARE=0, -DTPG_WENO_TG=2,
@@ -94,31 +95,7 @@ struct WenoArgs {
     double value;                          // the mask value (a T value held in a double)
 };
 
-// |x|: a sign clear
-__device__ __forceinline__ float abs_of(float x) { return __builtin_fabsf(x); }
-__device__ __forceinline__ double abs_of(double x) { return __builtin_fabs(x); }
-
-// R(q0, q1, q2, q3, q4) of the rule: q2 is the upwind cell, q3 the downwind one
-template <typename T>
-__device__ __forceinline__ T weno_face(T q0, T q1, T q2, T q3, T q4)
-{
-    constexpr T K13 = T(1) / T(3), K76 = T(7) / T(6), K116 = T(11) / T(6), K56 = T(5) / T(6), K16 = T(1) / T(6);
-    constexpr T K1312 = T(13) / T(12), K310 = T(3) / T(10), K35 = T(3) / T(5), K110 = T(1) / T(10);
-    constexpr T EPS = T(1e-8);
-    const T p2 = (K13 * q0 - K76 * q1) + K116 * q2;
-    const T p1 = (K56 * q2 - K16 * q1) + K13 * q3;
-    const T p0 = (K13 * q2 + K56 * q3) - K16 * q4;
-    const T s2 = (q0 - T(2) * q1) + q2, d2 = (q0 - T(4) * q1) + T(3) * q2;
-    const T s1 = (q1 - T(2) * q2) + q3, d1 = q1 - q3;
-    const T s0 = (q2 - T(2) * q3) + q4, d0 = (T(3) * q2 - T(4) * q3) + q4;
-    const T b2 = K1312 * (s2 * s2) + T(0.25) * (d2 * d2);
-    const T b1 = K1312 * (s1 * s1) + T(0.25) * (d1 * d1);
-    const T b0 = K1312 * (s0 * s0) + T(0.25) * (d0 * d0);
-    const T tau = abs_of(b0 - b2);
-    const T r0 = tau / (b0 + EPS), r1 = tau / (b1 + EPS), r2 = tau / (b2 + EPS);
-    const T a0 = K310 * (T(1) + r0 * r0), a1 = K35 * (T(1) + r1 * r1), a2 = K110 * (T(1) + r2 * r2);
-    return ((a0 * p0 + a1 * p1) + a2 * p2) / ((a0 + a1) + a2);
-}
+// R(q0, q1, q2, q3, q4) of the rule is weno_face (tpg_weno_face.hpp: the one definition, shared with tpg_weno_momentum.hip)
 
 // M * (M >= 0 ? R(x0, x1, x2, x3, x4) : R(x5, x4, x3, x2, x1)) for the six cells x0..x5 around the face between x2 and x3:
 // five selects (true for -0, false for NaN), one evaluation of R

@@ -31,7 +31,8 @@ interior on every side, corner halo cells included (u[Nx+1, 0], v[0, Ny+1]), and
 wide, and the halos of u, v and the horizontal halos of w are the caller's to fill first (the merged fill writes corners; continuity_plan
 fills w by default).  Only interior cells of Gu, Gv are written.  On an ImmersedBoundaryGrid the nodes k <= n_fc[i,j] of Gu and
 k <= n_cf[i,j] of Gv get 0 inside the same launch -- what mask_immersed_field leaves -- and everything is computed unmasked (Oceananigans'
-conditional operators beside an immersed node are out of scope).  The plan form holds its tensors: calling it enqueues on
+conditional operators beside an immersed node are out of scope).  The WENO5-upwinded vorticity term of the drivers is a call of its
+own, weno_momentum.py; this one keeps refusing every scheme but its own.  The plan form holds its tensors: calling it enqueues on
 torch's current stream and allocates nothing (usable inside torch.cuda.graph)."""
 from . import _lib
 from ._operator_plan import OperatorPlan, _check_fields, _ptr

@@ -15,7 +15,7 @@ ImmersedBoundaryGrid the nodes k <= n_cc[i,j] of G get 0 inside the same launch,
 
 Stays out: Oceananigans' drop of the reconstruction order beside the south wall and beside immersed nodes (in both drivers
 every row south of -78 degrees and both pole boxes are under the mask, so the rows this touches are masked in the workloads here);
-stretched-grid coefficients; WENO in z; other orders; WENOVectorInvariant for the momentum; latitude bands; the Julia hooks.
+stretched-grid coefficients; WENO in z; other orders; latitude bands; the Julia hooks.  The momentum half of the drivers' scheme is weno_momentum.py's.
 
 The plan form holds its tensors: calling it enqueues on torch's current stream and allocates nothing (usable inside torch.cuda.graph)."""
 from dataclasses import dataclass
