@@ -233,22 +233,34 @@ struct AtanRow { double p, q, r, s, hi, lo; };
 // ds_read_u8 instead of 4 compares + 4 selects.  The LUT sits behind the 30 row doubles (12 more doubles per copy).
 #define TPG_ATAN_ROWS_DOUBLES 30
 #define TPG_ATAN_TABLE_DOUBLES 42
+// The table as it lies in LDS, one constant image of TPG_ATAN_TABLE_DOUBLES 8-byte words: thread k copies word k, rows and LUT alike, so
+// the copy is ONE load and ONE store per thread with no row / column arithmetic and no branch (threads past the last word copy the last
+// word again: the same value to the same address).
 // LUT packed four bytes to a word: byte b = row offset of u = b (0 | 1..20 -> 48 | 21..46 -> 96 | 47..79 -> 144 | 80.. -> 192)
-__device__ const unsigned kAtanLutWords[24] = {
-    0x30303000u, 0x30303030u, 0x30303030u, 0x30303030u, 0x30303030u, 0x60606030u, 0x60606060u, 0x60606060u,
-    0x60606060u, 0x60606060u, 0x60606060u, 0x90606060u, 0x90909090u, 0x90909090u, 0x90909090u, 0x90909090u,
-    0x90909090u, 0x90909090u, 0x90909090u, 0x90909090u, 0xC0C0C0C0u, 0xC0C0C0C0u, 0xC0C0C0C0u, 0xC0C0C0C0u };
-TPG_DEV void atan_table_init(double* tab, int tid)
+struct AtanTableImage { double rows[5][6]; unsigned lut[24]; };
+static_assert(sizeof(AtanTableImage) == 8 * TPG_ATAN_TABLE_DOUBLES, "the image is the LDS table, word for word");
+__device__ const AtanTableImage kAtanTable = {
+    { { 1.0, 0.0, 1.0, 0.0, 0.0, 0.0 },                                        // [0, 0.4375): direct
+      { 2.0, 1.0, 2.0, 1.0, 0x1.dac670561bb4fp-2, 0x1.a2b7f222f65e2p-56 },     // [0.4375, 0.6875): (2x-1)/(2+x), atan(0.5)
+      { 1.0, 1.0, 1.0, 1.0, 0x1.921fb54442d18p-1, 0x1.1a62633145c07p-55 },     // [0.6875, 1.1875): (x-1)/(x+1),  atan(1)
+      { 1.0, 1.5, 1.0, 1.5, 0x1.f730bd281f69bp-1, 0x1.007887af0cbbdp-56 },     // [1.1875, 2.4375): (x-1.5)/(1+1.5x), atan(1.5)
+      { 0.0, 1.0, 0.0, 1.0, kPio2Hi, kPio2Lo } },                              // [2.4375, inf]:   -1/x, pi/2
+    { 0x30303000u, 0x30303030u, 0x30303030u, 0x30303030u, 0x30303030u, 0x60606030u, 0x60606060u, 0x60606060u,
+      0x60606060u, 0x60606060u, 0x60606060u, 0x90606060u, 0x90909090u, 0x90909090u, 0x90909090u, 0x90909090u,
+      0x90909090u, 0x90909090u, 0x90909090u, 0x90909090u, 0xC0C0C0C0u, 0xC0C0C0C0u, 0xC0C0C0C0u, 0xC0C0C0C0u } };
+// The copy in two halves, so that a kernel can issue the load first, do other work while it is in flight and store last.  tid >= 0.
+TPG_DEV unsigned atan_table_word(int tid) { return (unsigned)tid < TPG_ATAN_TABLE_DOUBLES - 1u ? (unsigned)tid : TPG_ATAN_TABLE_DOUBLES - 1u; }
+TPG_DEV unsigned long long atan_table_load(int tid)
 {
-    if (tid < 24) reinterpret_cast<unsigned*>(tab + TPG_ATAN_ROWS_DOUBLES)[tid] = kAtanLutWords[tid];
-    const double rows[5][6] = {
-        { 1.0, 0.0, 1.0, 0.0, 0.0, 0.0 },                                        // [0, 0.4375): direct
-        { 2.0, 1.0, 2.0, 1.0, 0x1.dac670561bb4fp-2, 0x1.a2b7f222f65e2p-56 },     // [0.4375, 0.6875): (2x-1)/(2+x), atan(0.5)
-        { 1.0, 1.0, 1.0, 1.0, 0x1.921fb54442d18p-1, 0x1.1a62633145c07p-55 },     // [0.6875, 1.1875): (x-1)/(x+1),  atan(1)
-        { 1.0, 1.5, 1.0, 1.5, 0x1.f730bd281f69bp-1, 0x1.007887af0cbbdp-56 },     // [1.1875, 2.4375): (x-1.5)/(1+1.5x), atan(1.5)
-        { 0.0, 1.0, 0.0, 1.0, kPio2Hi, kPio2Lo } };                              // [2.4375, inf]:   -1/x, pi/2
-    if (tid < TPG_ATAN_ROWS_DOUBLES) tab[tid] = rows[tid / 6][tid % 6];
+    unsigned long long v;
+    __builtin_memcpy(&v, reinterpret_cast<const char*>(&kAtanTable) + 8u * atan_table_word(tid), 8);
+    return v;
 }
+TPG_DEV void atan_table_store(double* tab, int tid, unsigned long long v)
+{
+    __builtin_memcpy(reinterpret_cast<char*>(tab) + 8u * atan_table_word(tid), &v, 8);
+}
+TPG_DEV void atan_table_init(double* tab, int tid) { atan_table_store(tab, tid, atan_table_load(tid)); }
 
 // atan(x), all x, with the interval constants taken from the LDS table (see atan_b for the
 // value-equivalence of dropping the msun early-outs).  p = 0 on the last interval: the numerator

@@ -41,8 +41,17 @@
 #include "tpg_common.hpp"
 #include "tpg_math.hpp"
 #include "tpg_batch.hpp"
+#include "tpg_tiles.hpp"
 
 using namespace tpgm;
+
+// Instruments of the tile kernel, scratch builds only (make GRID_FLAGS=-DTPG_CELLS_PROBE=n), never built into a library that a test or the
+// bench loads.  profiles/cells_floor: 1 store-only, 2 compute-only (values folded, one store per lane), 3 = 2 without the table loads;
+// results are WRONG by design.  profiles/cells_prologue: 4 = the prologue's load order of today with the index arithmetic of before (the
+// divisions by tiles_x, the per-lane test of wrap_col, sign-extended 64-bit table addresses); results are right.
+#ifndef TPG_CELLS_PROBE
+#define TPG_CELLS_PROBE 0
+#endif
 
 namespace {
 
@@ -417,13 +426,23 @@ struct RowTab { double shC, chC, shF, chF; };    // sinh/cosh(psi) of Center row
 // Scalar (s_load) read of the psi tables: the row index is wave-uniform and the tables were written by
 // the previous kernel, so they can be read through the constant address space into SGPRs -- no VGPRs,
 // and issued one row ahead so the latency never sits on the critical path.
+// The four entries are addressed as (table base) + (32-bit unsigned BYTE offset): the clamped rows are >= 1, so no index is negative and
+// none needs the sign-extended 64-bit address arithmetic that int indices cost (Ny < 2^27: the launcher checks).
 typedef const double __attribute__((address_space(4))) kconst_double;
+typedef const char __attribute__((address_space(4))) kconst_char;
 __device__ __forceinline__ RowTab load_rowtab(const GridK& g, int jc, int jf)
 {
-    kconst_double* tj = (kconst_double*)g.tj;
     jc = __builtin_amdgcn_readfirstlane(jc < 1 ? 1 : (jc > g.Ny ? g.Ny : jc));
     jf = __builtin_amdgcn_readfirstlane(jf < 1 ? 1 : (jf > g.Ny ? g.Ny : jf));
+#if TPG_CELLS_PROBE == 4
+    kconst_double* tj = (kconst_double*)g.tj;
     return RowTab{ tj[2 * g.Ny + jc - 1], tj[3 * g.Ny + jc - 1], tj[0 * g.Ny + jf - 1], tj[1 * g.Ny + jf - 1] };
+#else
+    kconst_char* tj = (kconst_char*)g.tj;
+    const unsigned ny8 = 8u * (unsigned)g.Ny, c8 = 8u * (unsigned)(jc - 1), f8 = 8u * (unsigned)(jf - 1);
+    auto at = [&](unsigned boff) -> double { return *(kconst_double*)(tj + boff); };
+    return RowTab{ at(2u * ny8 + c8), at(3u * ny8 + c8), at(f8), at(ny8 + f8) };
+#endif
 }
 
 __device__ __forceinline__ void points_fast(const GridK& g, const LaneConst& lc, const RowTab& rt, Step4& s, const double* atab)
@@ -568,8 +587,9 @@ __device__ __forceinline__ void points_pair(const GridK& g, const LaneConst& lc,
     s.X[1] = cl[1] * cp[1]; s.Y[1] = sl[1] * cp[1]; s.Z[1] = sp[1];      // FF
 }
 
-// stored column of a strip lane, wrapped into 1..Nx (more than one period away only on grids narrower than a strip)
-__device__ __forceinline__ int wrap_col(int v, int Nx)
+// stored column of a strip lane, wrapped into 1..Nx: tpgt::wrap_col (tpg_tiles.hpp).  This is the form of before, whose test for the
+// generic modulo is per lane; only the probe TPG_CELLS_PROBE = 4 still uses it.
+__device__ __forceinline__ int wrap_col_per_lane(int v, int Nx)
 {
     if (v < 1) v += Nx;
     if (v > Nx) v -= Nx;
@@ -658,9 +678,7 @@ __device__ __forceinline__ void hav_batch(const Nb (&X)[N], const Nb (&Y)[N], do
 // floor at sustained clocks (profiles/cells_floor: the kernel with its arithmetic removed takes 97 % of the full kernel's time), so
 // the order hands every XCD runs of 8 adjacent tiles: the shared lines meet in one L2.  (The persistent tile loop measured there is
 // not in the tree: slower by 8 %.)
-#ifndef TPG_CELLS_PROBE
-#define TPG_CELLS_PROBE 0      // instruments of profiles/cells_floor (scratch builds only: make GRID_FLAGS=-DTPG_CELLS_PROBE=n): 1 store-only,
-#endif                         // 2 compute-only (values folded, one store per lane), 3 = 2 without the table loads; results are WRONG by design
+// (TPG_CELLS_PROBE: see the top of the file)
 #if TPG_CELLS_PROBE == 2 || TPG_CELLS_PROBE == 3
 #define TPG_EMIT(A, OFF, V) (fold ^= (unsigned long long)__double_as_longlong(V) + (A), fold_off = (OFF), folded = true)
 #define TPG_EMIT_PINNED(A, OFF, V) TPG_EMIT(A, OFF, V)
@@ -669,33 +687,41 @@ __device__ __forceinline__ void hav_batch(const Nb (&X)[N], const Nb (&Y)[N], do
 #define TPG_EMIT_PINNED(A, OFF, V) put32<T, NT, false>(o, A, OFF, V)      // OFF left pin_off() in this basic block
 #endif
 
-// XCD-grouped order: a permutation inside every whole group of 64 block ids that gives the ids with one value of id mod 8 -- one XCD's
-// blocks -- 8 consecutive tiles; the ids of a last, partial group keep their own tile.  grouped = false: the identity (TPG_CELLS_ORDER 0)
-__device__ __forceinline__ int tile_of_block(int b, int tiles, bool grouped)
-{
-    const int base = b & ~63;
-    if (grouped && base + 64 <= tiles) return base + (b & 7) * 8 + ((b >> 3) & 7);
-    return b;
-}
+// The XCD-grouped order itself is tpgt::tile_of_block, and tile -> (tile row, tile column) tpgt::tile_xy (tpg_tiles.hpp).
+//
+// What the launch fixes comes from the host: tiles_y, and the reciprocal of tiles_x that replaces the wave's divisions (tpgt::divmod_rcp)
+struct TileArgs { int tiles_x, tiles, grouped, tiles_y; unsigned tiles_x_rcp; };
 
+// ---- the prologue: two load round trips per wave ---------------------------------------------------------------------------------
+// Before its first Float64 instruction a wave needs its kernel arguments, its word of the atan table (one constant image, see
+// tpgb::kAtanTable), four lambda-table entries per lane and four psi-table entries per wave.  Only the table entries need something that
+// was loaded -- the arguments -- so two round trips suffice: (1) the arguments and the atan word, issued together at the top;
+// (2) the table entries, issued as soon as the tile and the column are known.  The atan word goes to LDS only after (2) is in
+// flight, and the values of (2) are pinned around that store (empty asm statements), in front of the wave-uniform branch between the
+// paired and the general path: left alone, the compiler sinks loads whose only reader is the paired path into that branch, behind every
+// wait in front of it.  Nothing in front of the table loads may be a branch, either: the argument loads are sunk across block
+// boundaries, and each sunk group is a round trip of its own.  (Before: the atan copy was two exec-masked branches with a wait in
+// each, then three argument loads with a wait each, then the table loads.  profiles/cells_prologue/README.md has the instruction
+// listings and what the change measured.)
 template <typename T, bool NT, int R>
-__global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, int tiles_x, int tiles, int grouped)
+__global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, TileArgs ta)
 {
     __shared__ __attribute__((aligned(16))) double atabs[R][TPG_ATAN_TABLE_DOUBLES];
     __shared__ TileLds<R> lds;
     const int lane = threadIdx.x & 63;
     const int p = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);         // point row of this wave
-    // one copy of the atan interval table per wave: its load overlaps the lane's other table loads and
-    // needs no block barrier (LDS operations of one wave execute in order)
+    // one copy of the atan interval table per wave: needs no block barrier (LDS operations of one wave execute in order)
     double* atab = atabs[p];
-    tpgb::atan_table_init(atab, lane);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const unsigned long long atab_word = tpgb::atan_table_load(lane);       // round trip 1, with the kernel arguments
+    const int tiles_x = ta.tiles_x, tiles = ta.tiles, grouped = ta.grouped;
     // Tiles are counted tx fastest, tile rows NORTH to SOUTH, so that the one slow row of a launch -- row Ny, whose wave takes the
     // general (scalar) path through coord(): +2.2 us of block latency -- starts first instead of ending the launch.  Worth ~0.3 % at
     // 1/10 degree (in-process A/B, round 4: 505.7 -> 504.2 us per build, i.e. inside the noise); kept because it costs nothing.
+#if TPG_CELLS_PROBE == 4
     const int tiles_y = tiles / tiles_x;
+#else
+    const int tiles_y = ta.tiles_y;
+#endif
     // columns: lanes 0-31 ascend from shift + 30 tx (lane 1 of tile 0 is f1 = shift + 1, the column of lambda = -180), lanes 32-63 hold
     // the Center images 2 shift + 1 - (column of lane 63 - l), ascending as well, so lane +- 1 is the east / west neighbour inside
     // each half; all wrapped into 1..Nx, every lane evaluates a valid column.  The pair index kk < Nx / 2 guards a partial last tile.
@@ -706,24 +732,66 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, in
     unsigned long long fold = 0; unsigned fold_off = 0; bool folded = false;
 #endif
 
-    const int t = tile_of_block((int)blockIdx.x, tiles, grouped != 0);
+    const int t = tpgt::tile_of_block((int)blockIdx.x, tiles, grouped != 0);
+#if TPG_CELLS_PROBE == 4
     const int ty = tiles_y - 1 - t / tiles_x, tx = t % tiles_x;
+#else
+    const tpgt::TileXY txy = tpgt::tile_xy(t, tiles_x, tiles_y, ta.tiles_x_rcp);
+    const int ty = txy.ty, tx = txy.tx;
+#endif
     const int s0 = g.jm_lo - 1 + ty * (R - 1);
     const int s = s0 + p;                                                    // this wave's step
-    const int i = wrap_col(lane >= 32 ? g.shift - 30 * tx - 30 + hl : g.shift + 30 * tx + hl, g.Nx);
-    const bool col_emit = hl >= 1 && hl <= 30 && 30 * tx + (lane >= 32 ? 30 - hl : hl - 1) < g.Nx / 2;
-    const bool active_row = s <= g.jm_hi;                                    // rows past the band: idle waves
-    const unsigned col = (unsigned)(i + g.Hx - 1);
-    auto rowoff = [&](int j) -> unsigned { return (col + (unsigned)g.sx * (unsigned)(j - g.jstart + g.Hy)) * (unsigned)sizeof(T); };   // bytes
+    // a select of two wave-uniform values as mask arithmetic: written as ?:, it becomes an exec-masked branch, and every branch in front
+    // of the table loads is a block boundary that the loads of the arguments are sunk across
+    const int colA = g.shift + 30 * tx, colB = g.shift - 30 * tx - 30;     // scalar
+    const int icol = colA + ((colB - colA) & -(lane >> 5)) + hl;
+    asm volatile("" :: "s"(g.ti), "s"(g.tj));                                // every argument of round trip 1 is loaded HERE, in the entry block
+#if TPG_CELLS_PROBE == 4
+    const int i = wrap_col_per_lane(icol, g.Nx);
+#else
+    const int i = tpgt::wrap_col(icol, g.Nx);
+#endif
     LaneConst lc;
 #if TPG_CELLS_PROBE == 3
     const RowTab rt = RowTab{ 0.5 + 1e-3 * (s & 7), 1.1, 0.6, 1.2 };
     lc.aslF = 0.31 + 0.01 * hl; lc.aclF = 0.72 + 1e-3 * (i & 1); lc.aslC = 0.33 + 0.01 * hl; lc.aclC = 0.74;
 #else
-    const RowTab rt = load_rowtab(g, s, s + 1);                              // clamped: loaded whether or not the wave takes the fast path
+    // round trip 2: the table entries
+    RowTab rt = load_rowtab(g, s, s + 1);                                    // clamped: loaded whether or not the wave takes the fast path
+#if TPG_CELLS_PROBE == 4
     lc.aslF = g.ti[0 * g.Nx + i - 1]; lc.aclF = g.ti[1 * g.Nx + i - 1];      // every lane's column is a valid one
     lc.aslC = g.ti[2 * g.Nx + i - 1]; lc.aclC = g.ti[3 * g.Nx + i - 1];
+#else
+    {
+        // (uniform table base) + (32-bit unsigned byte offset in a VGPR), the saddr form, as the stores: i >= 1, and 32 Nx < 2^32 (the launcher checks)
+        const char* ti = reinterpret_cast<const char*>(g.ti);
+        const unsigned nx8 = 8u * (unsigned)g.Nx, i8 = 8u * (unsigned)(i - 1);
+        auto at = [&](unsigned boff) -> double { return *reinterpret_cast<const double*>(ti + boff); };
+        lc.aslF = at(i8); lc.aclF = at(i8 + nx8); lc.aslC = at(i8 + 2u * nx8); lc.aclC = at(i8 + 3u * nx8);
+    }
 #endif
+#endif
+#if TPG_CELLS_PROBE != 3
+    // The psi entries are pinned HERE, in front of the store: left to the compiler, the four scalar loads are issued only behind the store
+    // and its wait (a load from constant memory moves freely across the fences below, towards its reader).  The pin is no instruction but
+    // it is a wait: for round trip 2, which the first product needs whole anyway.
+    asm volatile("" : "+s"(rt.shC), "+s"(rt.chC), "+s"(rt.shF), "+s"(rt.chF));
+#endif
+    // the atan table goes to LDS now (LDS operations of one wave execute in order: no block barrier)
+    tpgb::atan_table_store(atab, lane, atab_word);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#if TPG_CELLS_PROBE != 3
+    // pins the lambda entries in front of the branch below (see "the prologue" above); no instruction, and the paired path's first
+    // products read these registers next
+    asm volatile("" : "+v"(lc.aslF), "+v"(lc.aclF), "+v"(lc.aslC), "+v"(lc.aclC));
+#endif
+    // no && here: a short-circuit is a branch per term
+    const bool col_emit = ((unsigned)(hl - 1) < 30u) & (30 * tx + (lane >= 32 ? 30 - hl : hl - 1) < g.Nx / 2);
+    const bool active_row = s <= g.jm_hi;                                    // rows past the band: idle waves
+    const unsigned col = (unsigned)(i + g.Hx - 1);
+    auto rowoff = [&](int j) -> unsigned { return (col + (unsigned)g.sx * (unsigned)(j - g.jstart + g.Hy)) * (unsigned)sizeof(T); };   // bytes
 
     // ---- phase 1: one point set per thread
     Step4 q;
@@ -1031,12 +1099,14 @@ int launch_build(const GridK& g, const OutPtrs& o, const HaloRegions& h, hipStre
     const int tiles_y = (nrows + (R - 1) - 1) / (R - 1);
     const bool offsets32 = (unsigned long long)g.sx * (unsigned long long)(g.jend - g.jstart + 1 + 2 * g.Hy) * sizeof(T) < (1ull << 32);
     const bool south_in_band = g.jstart - g.Hy <= 1;
-    const bool tile = cfg.cells_variant != 0 && tiles_y <= 65535 && offsets32;     // the sizes that took the tile kernel when tile rows rode on gridDim.y; stores use 32-bit byte offsets
+    const bool tables32 = g.Nx < (1 << 27) && g.Ny < (1 << 27);                    // the tile kernel reads its tables at 32-bit byte offsets: 4 x 8 Nx, 4 x 8 Ny
+    const bool tile = cfg.cells_variant != 0 && tiles_y <= 65535 && offsets32 && tables32;     // the sizes that took the tile kernel when tile rows rode on gridDim.y; stores use 32-bit byte offsets
     if (tile) {
         const int tiles_x = (g.Nx / 2 + 29) / 30;                  // two strips of 30 emitting columns per wave: a lambda -> -lambda pair
-        const int tiles = tiles_x * tiles_y;
-        if (nt) hipLaunchKernelGGL((k_cells_tile<T, true, R>), dim3((unsigned)tiles), dim3(64 * R), 0, s, g, o, tiles_x, tiles, cfg.cells_order);
-        else    hipLaunchKernelGGL((k_cells_tile<T, false, R>), dim3((unsigned)tiles), dim3(64 * R), 0, s, g, o, tiles_x, tiles, cfg.cells_order);
+        const int tiles = tiles_x * tiles_y;                       // far below 2^31: offsets32 bounds Nx x rows by 2^30, a tile emits up to 60 x 7 cells
+        const TileArgs ta = { tiles_x, tiles, cfg.cells_order, tiles_y, tpgt::rcp_of((unsigned)tiles_x) };
+        if (nt) hipLaunchKernelGGL((k_cells_tile<T, true, R>), dim3((unsigned)tiles), dim3(64 * R), 0, s, g, o, ta);
+        else    hipLaunchKernelGGL((k_cells_tile<T, false, R>), dim3((unsigned)tiles), dim3(64 * R), 0, s, g, o, ta);
     }
     else if (nt) hipLaunchKernelGGL((k_cells<T, true>), grid1, dim3(256), 0, s, g, o);
     else         hipLaunchKernelGGL((k_cells<T, false>), grid1, dim3(256), 0, s, g, o);

@@ -34,7 +34,7 @@ def main():
     sys.path.insert(0, ROOT)
     from bench_common import sources_sha16
     csrc = "orthogonalsphericalshellgrids.jl_amd/csrc/"
-    grid_src = [csrc + f for f in ("tpg_grid.hip", "tpg_batch.hpp", "tpg_math.hpp")]
+    grid_src = [csrc + f for f in ("tpg_grid.hip", "tpg_batch.hpp", "tpg_math.hpp", "tpg_tiles.hpp")]
     # the launch layer is part of the key: launch geometry decides traffic as much as kernel text does
     fill_src = [csrc + f for f in ("tpg_zipper_kernels.hpp", "tpg_launch.hpp", "tpg_zipper.hip")]
     sources = {"k_tables": grid_src, "k_cells_tile": grid_src, "k_cells": grid_src, "k_halos": grid_src, "k_south": grid_src,
