@@ -72,7 +72,8 @@ const char *tpg_weno_last_error(void);
  *   the results are bit-identical however the tracers are grouped.
  * - Stays out.  Oceananigans' drop of the reconstruction order beside the south wall and beside immersed nodes (in both drivers every
  *   row south of -78 degrees and both pole boxes are under the mask, so the rows this touches are masked in the workloads here);
- *   stretched-grid coefficients; WENO in z; other orders; latitude bands; the Julia hooks (the momentum half: include/tripolar_hip_weno_momentum.h).
+ *   stretched-grid coefficients; other orders; latitude bands; the Julia hooks (the momentum half: include/tripolar_hip_weno_momentum.h;
+ *   WENO in z: include/tripolar_hip_weno_xyz.h, a call of its own).
  *
  * Arrays
  * - c[q], G[q], u at (Face, Center, Center) and v at (Center, Face, Center): padded parents of ONE geometry (Nx, Ny, Nz, Hx, Hy, Hz).

@@ -39,5 +39,6 @@ from .weno import (WENO, Centered, FluxFormAdvection, WenoTracerAdvectionPlan, w
                    weno_tracer_advection_tendency)
 from .weno_momentum import (DefaultStencil, EnergyConserving, EnstrophyConserving, VectorInvariant, VelocityStencil, WenoMomentumAdvectionPlan,
                             WENOVectorInvariant, weno_momentum_advection_plan, weno_momentum_advection_tendency)
+from .weno_xyz import WenoXyzTracerAdvectionPlan, weno_xyz_tracer_advection_plan, weno_xyz_tracer_advection_tendency
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

@@ -1,6 +1,7 @@
 // tpg_weno_face.hpp -- the fifth-order WENO face value, the ONE definition in the tree: R(q0..q4) of include/tripolar_hip_weno.h
 // (k_weno_tracer_advection, tpg_weno.hip) and W5(q0..q4) of include/tripolar_hip_weno_momentum.h (k_weno_momentum_advection,
-// tpg_weno_momentum.hip), operation for operation, in the field type T with no contraction.
+// tpg_weno_momentum.hip), operation for operation, in the field type T with no contraction.  Beside it weno_face3, R3(q0..q2) of
+// include/tripolar_hip_weno_xyz.h, and the order table of that header's z-faces (k_weno_xyz_tracer_advection, tpg_weno_xyz.hip).
 // [recalled: uniform-grid coefficients, Jiang-Shu smoothness indicators, WENO-Z weights, eps = 1e-8; parity unpinned, like every operator here]
 #pragma once
 
@@ -30,6 +31,31 @@ __device__ __forceinline__ T weno_face(T q0, T q1, T q2, T q3, T q4)
     const T r0 = tau / (b0 + EPS), r1 = tau / (b1 + EPS), r2 = tau / (b2 + EPS);
     const T a0 = K310 * (T(1) + r0 * r0), a1 = K35 * (T(1) + r1 * r1), a2 = K110 * (T(1) + r2 * r2);
     return ((a0 * p0 + a1 * p1) + a2 * p2) / ((a0 + a1) + a2);
+}
+
+// R3(q0, q1, q2) of include/tripolar_hip_weno_xyz.h, the face value of order three: q1 is the upwind cell, q2 the downwind one
+template <typename T>
+__device__ __forceinline__ T weno_face3(T q0, T q1, T q2)
+{
+    constexpr T K23 = T(2) / T(3), K13 = T(1) / T(3);
+    constexpr T EPS = T(1e-8);
+    const T p1 = T(1.5) * q1 - T(0.5) * q0;
+    const T p0 = T(0.5) * (q1 + q2);
+    const T e1 = q1 - q0, b1 = e1 * e1;
+    const T e0 = q2 - q1, b0 = e0 * e0;
+    const T tau = abs_of(b0 - b1);
+    const T r0 = tau / (b0 + EPS), r1 = tau / (b1 + EPS);
+    const T a0 = K23 * (T(1) + r0 * r0), a1 = K13 * (T(1) + r1 * r1);
+    return (a0 * p0 + a1 * p1) / (a0 + a1);
+}
+
+// the order table of that header's z-faces: face f = 1 .. Nz + 1 lies between the levels f - 1 and f, and its order depends on its distance
+// from the nearer wall only -- 0: the centred mean (WENO_Z_CENTRED), 1: order 1, 2: order 3, 3 and more: order 5
+enum { WENO_Z_CENTRED = 0, WENO_Z_ORDER1 = 1, WENO_Z_ORDER3 = 2, WENO_Z_ORDER5 = 3 };
+__host__ __device__ __forceinline__ int weno_z_face_class(int f, int Nz)
+{
+    const int dist = f - 1 < Nz + 1 - f ? f - 1 : Nz + 1 - f;
+    return dist < WENO_Z_ORDER5 ? dist : WENO_Z_ORDER5;
 }
 
 }  // namespace

@@ -15,7 +15,7 @@ ImmersedBoundaryGrid the nodes k <= n_cc[i,j] of G get 0 inside the same launch,
 
 Stays out: Oceananigans' drop of the reconstruction order beside the south wall and beside immersed nodes (in both drivers
 every row south of -78 degrees and both pole boxes are under the mask, so the rows this touches are masked in the workloads here);
-stretched-grid coefficients; WENO in z; other orders; latitude bands; the Julia hooks.  The momentum half of the drivers' scheme is weno_momentum.py's.
+stretched-grid coefficients; other orders; latitude bands; the Julia hooks.  WENO in z is weno_xyz.py's call, not this one's.  The momentum half of the drivers' scheme is weno_momentum.py's.
 
 The plan form holds its tensors: calling it enqueues on torch's current stream and allocates nothing (usable inside torch.cuda.graph)."""
 from dataclasses import dataclass
@@ -64,8 +64,9 @@ class WenoTracerAdvectionPlan(_TracerTendencyPlan):
     @staticmethod
     def _refuse(scheme, what):
         if not isinstance(scheme, FluxFormAdvection) or scheme != BUILT:
+            all_weno = scheme in (WENO(order=5), FluxFormAdvection(WENO(order=5), WENO(order=5), WENO(order=5)))
             raise NotImplementedError(f"{what}: advection scheme {scheme!r} is not built ({_BUILT_NAME} is: WENO of order 5 in x and y, "
-                                      "Centered() in z)")
+                                      "Centered() in z)" + ("; weno_xyz_tracer_advection_tendency has WENO of order 5 in all three" if all_weno else ""))
 
     @staticmethod
     def _extra(scheme):
