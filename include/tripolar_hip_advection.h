@@ -73,7 +73,10 @@ const char *tpg_advection_last_error(void);
  *  6. a pointer off its element alignment (the message names it), n_cc off int32 alignment: TPG_ERR_INVALID_ARGUMENT;
  *  7. any G[q] overlapping any c[p], u, v, w (whose parent is one level longer) or another G: TPG_ERR_INVALID_ARGUMENT;
  *  8. Hx < 1, Hy < 1 or Hz < 1: TPG_ERR_UNSUPPORTED;
- *  9. more work items than 32 bits index: TPG_ERR_UNSUPPORTED. */
+ *  9. more work items than 32 bits index: TPG_ERR_UNSUPPORTED.
+ * Everything else is served, down to (Nx, Ny, Nz) = (2, 1, 1) at halo (1, 1, 1) -- one chunk, one row, one level -- and up past 2^31
+ * elements a parent (8640 x 4320 x 64 at halo 4, with n_cc); a latitude band down to Hy rows gives the rows of the global call
+ * (tests/test_gpu_tendency_edges.py). */
 int tpg_tracer_advection_tendency(const void *const *c, void *const *G, int nfields, const void *u, const void *v, const void *w,
                                   const void *dy_fc, const void *dx_cf, const void *az_cc, const void *dz_c, const int32_t *n_cc,
                                   double mask_value, int scheme, int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);

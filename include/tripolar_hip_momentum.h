@@ -89,7 +89,10 @@ const char *tpg_momentum_last_error(void);
  *  5. a pointer off its element alignment, a count plane off int32 alignment: TPG_ERR_INVALID_ARGUMENT;
  *  6. Gu or Gv overlapping u, v, w (whose parent is one level longer) or each other: TPG_ERR_INVALID_ARGUMENT;
  *  7. Hx < 1, Hy < 1 or Hz < 1: TPG_ERR_UNSUPPORTED;
- *  8. more work items than 32 bits index: TPG_ERR_UNSUPPORTED. */
+ *  8. more work items than 32 bits index: TPG_ERR_UNSUPPORTED.
+ * Everything else is served, down to (Nx, Ny, Nz) = (2, 1, 1) at halo (1, 1, 1) -- one chunk, one row, one level -- and up past 2^31
+ * elements a parent (8640 x 4320 x 64 at halo 4, with n_fc, n_cf); a latitude band down to Hy rows gives the rows of the global call
+ * (tests/test_gpu_tendency_edges.py). */
 int tpg_momentum_advection_tendency(const void *u, const void *v, const void *w, void *Gu, void *Gv,
                                     const void *dx_fc, const void *dy_fc, const void *az_fc, const void *dx_cf, const void *dy_cf,
                                     const void *az_cf, const void *az_cc, const void *az_ff, const void *dz_f, const int32_t *n_fc,

@@ -78,7 +78,10 @@ const char *tpg_weno_momentum_last_error(void);
  *  4. a pointer off its element alignment, a count plane off int32 alignment: TPG_ERR_INVALID_ARGUMENT;
  *  5. Gu or Gv overlapping u, v, w (whose parent is one level longer) or each other: TPG_ERR_INVALID_ARGUMENT;
  *  6. Hx < 3, Hy < 3 or Hz < 1: TPG_ERR_UNSUPPORTED, the message names the stencil and the halo passed;
- *  7. more work items than 32 bits index: TPG_ERR_UNSUPPORTED. */
+ *  7. more work items than 32 bits index: TPG_ERR_UNSUPPORTED.
+ * Everything else is served, down to (Nx, Ny, Nz) = (4, 3, 1) at halo (3, 3, 1) -- Nx = Hx + 1, Ny = Hy: the arms end on the last halo
+ * cell -- and (4, 4, 5) at halo (4, 4, 4), and up past 2^31 elements a parent (8640 x 4320 x 64 at halo 4, with n_fc, n_cf); a latitude
+ * band down to Hy rows gives the rows of the global call (tests/test_gpu_tendency_edges.py). */
 int tpg_weno_momentum_advection_tendency(const void *u, const void *v, const void *w, void *Gu, void *Gv,
                                          const void *dx_fc, const void *dy_fc, const void *az_fc, const void *dx_cf, const void *dy_cf,
                                          const void *az_cf, const void *az_cc, const void *az_ff, const void *dz_f, const int32_t *n_fc,

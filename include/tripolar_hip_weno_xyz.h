@@ -78,7 +78,10 @@ const char *tpg_weno_xyz_last_error(void);
  *  6. any G[q] overlapping any c[p], u, v, w (whose parent is one level longer) or another G: TPG_ERR_INVALID_ARGUMENT;
  *  7. Hx < 3, Hy < 3 or Hz < 1: TPG_ERR_UNSUPPORTED, the message names the stencil
  *     "c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-3..k+3 within 0..Nz+1]" and the halo passed;
- *  8. more work items than 32 bits index: TPG_ERR_UNSUPPORTED. */
+ *  8. more work items than 32 bits index: TPG_ERR_UNSUPPORTED.
+ * Everything else is served, down to (Nx, Ny, Nz) = (4, 3, 1) at halo (3, 3, 1) -- Nx = Hx + 1, Ny = Hy: the arms end on the last halo
+ * cell -- and (4, 4, 1) at halo (4, 4, 4), one chunk per row, and up past 2^31 elements a parent (8640 x 4320 x 64 at halo 4, with n_cc);
+ * a latitude band down to Hy rows gives the rows of the global call (tests/test_gpu_tendency_edges.py). */
 int tpg_weno_xyz_tracer_advection_tendency(const void *const *c, void *const *G, int nfields, const void *u, const void *v, const void *w,
                                            const void *dy_fc, const void *dx_cf, const void *az_cc, const void *dz_c, const int32_t *n_cc,
                                            double mask_value, int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void *stream);
