@@ -1,6 +1,6 @@
 // tpg_operator.hpp -- what the operator translation units share (tpg_operators.hip, tpg_continuity.hip, tpg_barotropic.hip,
-// tpg_free_surface.hip, tpg_timestep.hip, tpg_momentum.hip, tpg_weno_momentum.hip and, through tpg_tracer_tendency.hpp, tpg_advection.hip and tpg_weno.hip; each is
-// a library of its own): the chunk and count access types and the store of their kernels, and the arithmetic, the Span record and the overlap
+// tpg_free_surface.hip, tpg_timestep.hip and, through tpg_tracer_tendency.hpp, tpg_advection.hip, tpg_weno.hip and tpg_weno_xyz.hip, through
+// tpg_momentum_tendency.hpp, tpg_momentum.hip and tpg_weno_momentum.hip; each is a library of its own): the chunk and count access types and the store of their kernels, and the arithmetic, the Span record and the overlap
 // check their entry points check arguments with.  An entry point keeps its own sequence of checks, statuses and messages; a new operator
 // starts here.
 #pragma once
@@ -42,7 +42,7 @@ bool arrays_overlap(const void* p, unsigned long long pbytes, const void* q, uns
 struct Span { const void* p; unsigned long long bytes; char name[24]; bool written; };
 
 // any written array against every other array of the call.  A call whose messages or order differ keeps its own loop (the tracer tendencies,
-// tpg_tracer_tendency.hpp; tpg_momentum.hip)
+// tpg_tracer_tendency.hpp; the momentum tendencies, tpg_momentum_tendency.hpp)
 int check_overlaps(const Span* s, int n, const char* why)
 {
     for (int o = 0; o < n; ++o) {

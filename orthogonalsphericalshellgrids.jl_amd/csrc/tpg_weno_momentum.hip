@@ -43,7 +43,7 @@
 //
 // 16-B chunks where rows and pointers sit on the 16-B grid, the same chunks element-aligned otherwise: chunk_plan's plain / GEN split over
 // all the arrays passed.  Element offsets are 64-bit.  No atomics, no LDS, nothing allocated, no host wait.
-#include "tpg_operator.hpp"
+#include "tpg_momentum_tendency.hpp"
 #include "tpg_weno_face.hpp"
 #include "../../include/tripolar_hip_weno_momentum.h"
 
@@ -400,59 +400,12 @@ int tpg_weno_momentum_advection_tendency(const void* u, const void* v, const voi
                                          int Nx, int Ny, int Nz, int Hx, int Hy, int Hz, int ft, void* stream)
 {
     if (int rc = tpg::check_geom(Nx, Ny, Nz, Hx, Hy, Hz, ft)) return rc;
-    if (!u || !v || !w) { tpg::set_error("null u, v or w"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (!Gu || !Gv) { tpg::set_error("null Gu or Gv"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (!dx_fc || !dy_fc || !az_fc || !dx_cf || !dy_cf || !az_cf || !az_cc || !az_ff || !dz_f) {
-        tpg::set_error("null dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff or dz_f");
-        return TPG_ERR_INVALID_ARGUMENT;
-    }
-    if (!n_fc != !n_cf) { tpg::set_error("the count planes n_fc and n_cf are given together or not at all (%s is null)", n_fc ? "n_cf" : "n_fc"); return TPG_ERR_INVALID_ARGUMENT; }
-    const size_t esz = elem_size(ft);
-    if (misaligned(esz, u, v, w)) { tpg::set_error("u, v or w pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (misaligned(esz, Gu, Gv)) { tpg::set_error("Gu or Gv pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (misaligned(esz, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff, dz_f)) {
-        tpg::set_error("dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff or dz_f pointer not aligned to its element type");
-        return TPG_ERR_INVALID_ARGUMENT;
-    }
-    if ((uintptr_t)n_fc % 4 || (uintptr_t)n_cf % 4) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }
-    const Geom g = tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz);
-    const unsigned long long bytes = (unsigned long long)g.plane * (Nz + 2 * Hz) * esz;            // u, v, Gu, Gv
-    const unsigned long long wbytes = (unsigned long long)g.plane * (Nz + 1 + 2 * Hz) * esz;       // w: one more level
-    const Span in[3] = { { u, bytes, "u" }, { v, bytes, "v" }, { w, wbytes, "w" } };
-    const Span out[2] = { { Gu, bytes, "Gu" }, { Gv, bytes, "Gv" } };
-    for (const Span& o : out)
-        for (const Span& s : in)
-            if (arrays_overlap(o.p, o.bytes, s.p, s.bytes)) {
-                tpg::set_error("%s overlaps %s (every item reads cells while its neighbours write)", o.name, s.name);
-                return TPG_ERR_INVALID_ARGUMENT;
-            }
-    if (arrays_overlap(Gv, bytes, Gu, bytes)) { tpg::set_error("Gv overlaps Gu"); return TPG_ERR_INVALID_ARGUMENT; }
-    if (Hx < HALO || Hy < HALO || Hz < 1) {
-        tpg::set_error("the rule reads Z[i, j-2..j+3] and Z[i-2..i+3, j], that is u, v[i-3..i+3, j-3..j+3, k-1..k+1], and w[i-1, j], w[i, j-1]: "
-                       "Hx >= 3, Hy >= 3 and Hz >= 1 needed (halo (%d,%d,%d))", Hx, Hy, Hz);
-        return TPG_ERR_UNSUPPORTED;
-    }
-    const int JT = ft == TPG_F64 ? ROWS<double> : ROWS<float>;
-    const long long tiles = (Ny + JT - 1) / JT;
-    if (tiles * (Nx / 2) >= (1ll << 31) - 256) { tpg::set_error("momentum advection: too many work items for 32-bit indexing"); return TPG_ERR_UNSUPPORTED; }
-    const WmomPtrs p{ u, v, w, Gu, Gv, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff, dz_f, n_fc, n_cf };
-    void* arrays[13];
-    int na = 0;
-    for (const void* x : { u, v, w, (const void*)Gu, (const void*)Gv, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff }) arrays[na++] = const_cast<void*>(x);
-    hipStream_t st = tpg::as_stream(stream);
-    return dispatch_ft(ft, [&](auto ty) {
+    const MomentumCall call{ u, v, w, Gu, Gv, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff, dz_f, n_fc, n_cf, mask_value,
+                             tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz), ft };
+    if (int rc = call.check(HALO, "Z[i, j-2..j+3] and Z[i-2..i+3, j], that is u, v[i-3..i+3, j-3..j+3, k-1..k+1], and w[i-1, j], w[i, j-1]")) return rc;
+    return call.launch<WmomPtrs, WmomArgs>(ROWS<double>, ROWS<float>, "k_weno_momentum_advection", stream, [](auto ty, auto cw, auto gen, auto mask) {
         typedef decltype(ty) T;
-        const ChunkPlan cp = chunk_plan<T>(g, arrays, na);
-        const int cpr = Nx / cp.W;
-        const WmomArgs a{ Nx, Ny, Nz, g.sx, cpr, (int)(tiles * cpr), g.plane, interior2(g), interior3(g), n_fc ? (double)(T)mask_value : 0.0 };
-        const unsigned blocks = (unsigned)((a.items + 255) / 256);
-        dispatch_chunk<T>(cp.W, cp.gen, [&](auto cw, auto gen) {
-            constexpr int W = decltype(cw)::value;
-            constexpr bool GEN = decltype(gen)::value;
-            if (n_fc) hipLaunchKernelGGL((k_weno_momentum_advection<T, W, GEN, true, ROWS<T>, LOOKAHEAD<T>>), dim3(blocks), dim3(256), 0, st, p, a);
-            else      hipLaunchKernelGGL((k_weno_momentum_advection<T, W, GEN, false, ROWS<T>, LOOKAHEAD<T>>), dim3(blocks), dim3(256), 0, st, p, a);
-        });
-        return tpg::launch_status("k_weno_momentum_advection");
+        return k_weno_momentum_advection<T, decltype(cw)::value, decltype(gen)::value, decltype(mask)::value, ROWS<T>, LOOKAHEAD<T>>;
     });
 }
 

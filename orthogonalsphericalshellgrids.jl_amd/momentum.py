@@ -50,17 +50,15 @@ def _same(a, b):
     return a is b or a.data is b.data or a.data.data_ptr() == b.data.data_ptr()
 
 
-class MomentumAdvectionPlan(OperatorPlan):
-    """momentum_advection_tendency(u, v, w, out=(Gu, Gv)) with the arguments built once: `plan()` issues ONE
-    tpg_momentum_advection_tendency call on torch's current stream and then, with `fill_halos`, ONE HaloFillPlan of Gu and Gv.  It allocates
-    nothing when called and is a single chain of launches, so it replays inside torch.cuda.graph.  On an ImmersedBoundaryGrid with
-    `mask_immersed` the (Face, Center) and (Center, Face) count planes and the value 0 go into the call.  The plan holds the tensors of u, v,
-    w, Gu and Gv, the metric arrays, the spacings and the count planes: rebuild it if a field's `data` is replaced."""
+class _MomentumTendencyPlan(OperatorPlan):
+    """The plan of a vector-invariant momentum tendency, whatever the scheme: the checks of the fields, the metric arrays, ONE C call and the
+    halo fill of Gu and Gv.  A scheme's class (MomentumAdvectionPlan here, WenoMomentumAdvectionPlan in weno_momentum.py) supplies what
+    differs: `_refuse(scheme, what)`, the smallest halo `_HALO` with the sentence `_HALO_RULE` of its refusal, the band refusal's
+    `_BAND_ROWS`, `_LIBRARY` (the names in _lib of the loader and the checker, and the C function) and `_extra(scheme)`, the arguments
+    between the mask value and Nx."""
 
-    def __init__(self, u, v, w, Gu, Gv, *, scheme="enstrophy_conserving", mask_immersed=True, fill_halos=False, what="momentum_advection_plan"):
-        if scheme not in _SCHEMES:
-            raise NotImplementedError(f"{what}: momentum advection scheme {scheme!r} is not built ('enstrophy_conserving' is; the "
-                                      "energy-conserving and WENO vector-invariant schemes are not)")
+    def __init__(self, u, v, w, Gu, Gv, *, scheme, mask_immersed, fill_halos, what):
+        self._refuse(scheme, what)
         names = {"u": (u, _LOCS["u"]), "v": (v, _LOCS["v"]), "w": (w, _LOCS["w"]), "Gu": (Gu, _LOCS["u"]), "Gv": (Gv, _LOCS["v"])}
         first = _check_fields(names, what, "u, v, w, Gu and Gv")
         for name, g in (("Gu", Gu), ("Gv", Gv)):
@@ -69,24 +67,58 @@ class MomentumAdvectionPlan(OperatorPlan):
                     raise ValueError(f"{what}: {name} is {other} itself (every node reads its neighbours while they are written)")
         if _same(Gu, Gv):
             raise ValueError(f"{what}: Gu and Gv are one field")
-        if min(first.Hx, first.Hy, first.Hz) < 1:
-            raise ValueError(f"{what}: the rule reads one cell beyond the interior on every side: every halo must be at least 1 "
-                             f"(halo ({first.Hx}, {first.Hy}, {first.Hz}))")
+        if any(h < least for h, least in zip((first.Hx, first.Hy, first.Hz), self._HALO)):
+            raise ValueError(f"{what}: {self._HALO_RULE} (halo ({first.Hx}, {first.Hy}, {first.Hz}))")
         g = _bare(first.grid)
         if g.global_size and g.Ny != g.global_size[1]:
-            raise NotImplementedError(f"{what}: latitude-band grids are not handled: the row Ny + 1 of a band is the exchanged halo row, and "
-                                      "the band path of the momentum tendency is not tested yet")
+            raise NotImplementedError(f"{what}: latitude-band grids are not handled: {self._BAND_ROWS}, and the band path of the momentum "
+                                      "tendency is not tested yet")
         self.u, self.v, self.w, self.Gu, self.Gv, self.scheme = u, v, w, Gu, Gv, scheme
         dtype, device = u.data.dtype, u.data.device
-        lib = _lib.momentum_lib()
+        load, check, function = self._LIBRARY
+        function, check = getattr(getattr(_lib, load)(), function), getattr(_lib, check)
         counts = getattr(first.grid, "column_counts", None) if mask_immersed else None
         nfc, ncf = (None, None) if counts is None else (counts["fc"], counts["cf"])
         with _on_device(device):
             metrics = [_metric(g, name, dtype, device) for name in _METRICS]
             dz = _grid_table(g, "_z_all_face_spacings", z_all_face_spacings, dtype, device)
         held = [u.data, v.data, w.data, Gu.data, Gv.data, *metrics, dz, nfc, ncf]
-        args = (*(_ptr(t) for t in held), 0.0, _SCHEMES[scheme], u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
-        self._set_call(lib.tpg_momentum_advection_tendency, args, _lib.check_momentum, device, held, (Gu, Gv) if fill_halos else ())
+        args = (*(_ptr(t) for t in held), 0.0, *self._extra(scheme), u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
+        self._set_call(function, args, check, device, held, (Gu, Gv) if fill_halos else ())
+
+
+def _tendency_fields(u, out, what):
+    """the `out` of a one-shot call: as given, or a new pair of Fields at (Face, Center, Center) and (Center, Face, Center)"""
+    if out is not None:
+        return out
+    if not isinstance(u, Field) or u.loc != _LOCS["u"]:
+        raise TypeError(f"{what}: u must be a Field at (Face, Center, Center)")
+    return Field(_LOCS["u"], u.grid, name="Gu"), Field(_LOCS["v"], u.grid, name="Gv")
+
+
+class MomentumAdvectionPlan(_MomentumTendencyPlan):
+    """momentum_advection_tendency(u, v, w, out=(Gu, Gv)) with the arguments built once: `plan()` issues ONE
+    tpg_momentum_advection_tendency call on torch's current stream and then, with `fill_halos`, ONE HaloFillPlan of Gu and Gv.  It allocates
+    nothing when called and is a single chain of launches, so it replays inside torch.cuda.graph.  On an ImmersedBoundaryGrid with
+    `mask_immersed` the (Face, Center) and (Center, Face) count planes and the value 0 go into the call.  The plan holds the tensors of u, v,
+    w, Gu and Gv, the metric arrays, the spacings and the count planes: rebuild it if a field's `data` is replaced."""
+    _HALO = (1, 1, 1)
+    _HALO_RULE = "the rule reads one cell beyond the interior on every side: every halo must be at least 1"
+    _BAND_ROWS = "the row Ny + 1 of a band is the exchanged halo row"
+    _LIBRARY = ("momentum_lib", "check_momentum", "tpg_momentum_advection_tendency")
+
+    def __init__(self, u, v, w, Gu, Gv, *, scheme="enstrophy_conserving", mask_immersed=True, fill_halos=False, what="momentum_advection_plan"):
+        super().__init__(u, v, w, Gu, Gv, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos, what=what)
+
+    @staticmethod
+    def _refuse(scheme, what):
+        if scheme not in _SCHEMES:
+            raise NotImplementedError(f"{what}: momentum advection scheme {scheme!r} is not built ('enstrophy_conserving' is; the "
+                                      "energy-conserving and WENO vector-invariant schemes are not)")
+
+    @staticmethod
+    def _extra(scheme):
+        return (_SCHEMES[scheme],)
 
 
 def momentum_advection_plan(u, v, w, Gu, Gv, *, scheme="enstrophy_conserving", mask_immersed=True, fill_halos=False):
@@ -101,11 +133,7 @@ def momentum_advection_tendency(u, v, w, out=None, *, scheme="enstrophy_conservi
     On an ImmersedBoundaryGrid with `mask_immersed` the nodes under the bottom get 0.  Only the interiors are written; `fill_halos` then
     fills Gu and Gv.  Returns (Gu, Gv).  Builds a MomentumAdvectionPlan and runs it once; use momentum_advection_plan in a time loop."""
     what = "momentum_advection_tendency"
-    if out is None:
-        if not isinstance(u, Field) or u.loc != _LOCS["u"]:
-            raise TypeError(f"{what}: u must be a Field at (Face, Center, Center)")
-        out = (Field(_LOCS["u"], u.grid, name="Gu"), Field(_LOCS["v"], u.grid, name="Gv"))
-    Gu, Gv = out
+    Gu, Gv = _tendency_fields(u, out, what)
     plan = MomentumAdvectionPlan(u, v, w, Gu, Gv, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos, what=what)
     plan()
     return plan.Gu, plan.Gv

@@ -25,12 +25,7 @@ bands, the Julia hooks.
 The plan form holds its tensors: calling it enqueues on torch's current stream and allocates nothing (usable inside torch.cuda.graph)."""
 from dataclasses import dataclass
 
-from . import _lib
-from ._operator_plan import OperatorPlan, _check_fields, _ptr
-from .fields import Field
-from .momentum import _LOCS, _METRICS, _same
-from .reductions import _bare, _grid_table, _metric, z_all_face_spacings
-from .time_stepping import _on_device
+from .momentum import _MomentumTendencyPlan, _tendency_fields
 from .weno import WENO
 
 
@@ -88,41 +83,24 @@ def _refuse(scheme, what):
         raise NotImplementedError(f"{what}: momentum advection scheme {scheme!r} is not built ({_BUILT_NAME} is)")
 
 
-class WenoMomentumAdvectionPlan(OperatorPlan):
+class WenoMomentumAdvectionPlan(_MomentumTendencyPlan):
     """weno_momentum_advection_tendency(u, v, w, out=(Gu, Gv)) with the arguments built once: `plan()` issues ONE
     tpg_weno_momentum_advection_tendency call on torch's current stream and then, with `fill_halos`, ONE HaloFillPlan of Gu and Gv.  It
     allocates nothing when called and is a single chain of launches, so it replays inside torch.cuda.graph.  On an ImmersedBoundaryGrid
     with `mask_immersed` the (Face, Center) and (Center, Face) count planes and the value 0 go into the call.  The plan holds the tensors of
     u, v, w, Gu and Gv, the metric arrays, the spacings and the count planes: rebuild it if a field's `data` is replaced."""
+    _HALO = (3, 3, 1)
+    _HALO_RULE = "the rule reads three cells beyond the interior in x and y and one in z: the halo must be at least (3, 3, 1)"
+    _BAND_ROWS = "the rows Ny + 1 .. Ny + 3 of a band are exchanged halo rows"
+    _LIBRARY = ("weno_momentum_lib", "check_weno_momentum", "tpg_weno_momentum_advection_tendency")
+    _refuse = staticmethod(_refuse)
 
     def __init__(self, u, v, w, Gu, Gv, *, scheme=BUILT, mask_immersed=True, fill_halos=False, what="weno_momentum_advection_plan"):
-        _refuse(scheme, what)
-        names = {"u": (u, _LOCS["u"]), "v": (v, _LOCS["v"]), "w": (w, _LOCS["w"]), "Gu": (Gu, _LOCS["u"]), "Gv": (Gv, _LOCS["v"])}
-        first = _check_fields(names, what, "u, v, w, Gu and Gv")
-        for name, g in (("Gu", Gu), ("Gv", Gv)):
-            for other, f in (("u", u), ("v", v), ("w", w)):
-                if _same(g, f):
-                    raise ValueError(f"{what}: {name} is {other} itself (every node reads its neighbours while they are written)")
-        if _same(Gu, Gv):
-            raise ValueError(f"{what}: Gu and Gv are one field")
-        if first.Hx < 3 or first.Hy < 3 or first.Hz < 1:
-            raise ValueError(f"{what}: the rule reads three cells beyond the interior in x and y and one in z: the halo must be at least "
-                             f"(3, 3, 1) (halo ({first.Hx}, {first.Hy}, {first.Hz}))")
-        g = _bare(first.grid)
-        if g.global_size and g.Ny != g.global_size[1]:
-            raise NotImplementedError(f"{what}: latitude-band grids are not handled: the rows Ny + 1 .. Ny + 3 of a band are exchanged halo "
-                                      "rows, and the band path of the momentum tendency is not tested yet")
-        self.u, self.v, self.w, self.Gu, self.Gv, self.scheme = u, v, w, Gu, Gv, scheme
-        dtype, device = u.data.dtype, u.data.device
-        lib = _lib.weno_momentum_lib()
-        counts = getattr(first.grid, "column_counts", None) if mask_immersed else None
-        nfc, ncf = (None, None) if counts is None else (counts["fc"], counts["cf"])
-        with _on_device(device):
-            metrics = [_metric(g, name, dtype, device) for name in _METRICS]
-            dz = _grid_table(g, "_z_all_face_spacings", z_all_face_spacings, dtype, device)
-        held = [u.data, v.data, w.data, Gu.data, Gv.data, *metrics, dz, nfc, ncf]
-        args = (*(_ptr(t) for t in held), 0.0, u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
-        self._set_call(lib.tpg_weno_momentum_advection_tendency, args, _lib.check_weno_momentum, device, held, (Gu, Gv) if fill_halos else ())
+        super().__init__(u, v, w, Gu, Gv, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos, what=what)
+
+    @staticmethod
+    def _extra(scheme):
+        return ()
 
 
 def weno_momentum_advection_plan(u, v, w, Gu, Gv, *, scheme=BUILT, mask_immersed=True, fill_halos=False):
@@ -140,11 +118,7 @@ def weno_momentum_advection_tendency(u, v, w, out=None, *, scheme=BUILT, mask_im
     weno_momentum_advection_plan in a time loop."""
     what = "weno_momentum_advection_tendency"
     _refuse(scheme, what)
-    if out is None:
-        if not isinstance(u, Field) or u.loc != _LOCS["u"]:
-            raise TypeError(f"{what}: u must be a Field at (Face, Center, Center)")
-        out = (Field(_LOCS["u"], u.grid, name="Gu"), Field(_LOCS["v"], u.grid, name="Gv"))
-    Gu, Gv = out
+    Gu, Gv = _tendency_fields(u, out, what)
     plan = WenoMomentumAdvectionPlan(u, v, w, Gu, Gv, scheme=scheme, mask_immersed=mask_immersed, fill_halos=fill_halos, what=what)
     plan()
     return plan.Gu, plan.Gv

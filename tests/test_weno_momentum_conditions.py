@@ -265,6 +265,7 @@ def test_the_build_names_the_library_the_map_and_the_argcheck_tool():
         body = open(os.path.join(csrc, src)).read()
         assert '#include "tpg_weno_face.hpp"' in body and "T weno_face(" not in body
     assert open(os.path.join(csrc, "tpg_weno_face.hpp")).read().count("T weno_face(") == 1
-    tool = open(os.path.join(ROOT, "tools", "weno_momentum_argcheck.cpp")).read()
+    tool = open(os.path.join(ROOT, "tools", "momentum_argcheck.cpp")).read()                               # one program over both momentum calls
     assert "-Xarch_host -fsanitize=address,undefined" in tool and "int main()" in tool and "tpg_weno_momentum_advection_tendency" in tool
+    assert "tpg_momentum_advection_tendency" in tool and "csrc/tpg_momentum.hip" in tool and "csrc/tpg_weno_momentum.hip" in tool
     assert "MOMENTUM_TENDENCY_LIBRARIES" in open(os.path.join(ROOT, "__graft_entry__.py")).read()          # build() loads it
