@@ -359,6 +359,32 @@ template <int N, bool POS = false> TPG_DEV bool atan_small_b(const double (&x)[N
     return TPG_RARE(rare);
 }
 
+// atan(x) for +0 <= x < 2^-14: atan_small_b<N, true> with the Horner steps that are the identity there left out.  The tile kernel's first
+// tier: on any grid finer than about 0.9 degrees every triangle tangent of a cell (~ a quarter of the cell's solid angle) lies below it.
+// atan_small_b ends its two chains in w = t^4 with s1 = fma(w, s1', aT0), aT0 = 3.33333333333329318027e-01, and s2' = fma(w, s2'', aT1),
+// aT1 = -1.99999999998764832476e-01.  fma(w, s, c) = RN(c + w s) is c whenever |w s| < ulp(c) / 2 and c is no power of two:
+//   aT0 in [2^-2, 2^-1): half an ulp is 2^-55;  0 < s1' < 0.15 (a sum of positive terms, at most 0.1429 + w 0.091 + ...);
+//   |aT1| in [2^-3, 2^-2): half an ulp is 2^-56;  |s2''| < 0.112;
+//   t < 2^-14 gives w < 2^-56, so |w s1'| < 2^-58.7 and |w s2''| < 2^-59.1: margins of more than 2^3 on both.
+// So s1 = aT0 and s2' = aT1 exactly, the eight fma in front of them are dead, and what is left -- z, w, s2 = w aT1, sm = z aT0 + s2,
+// r = t - t sm, in atan_small_b's order -- has the bits of atan_small_b<N, true> (= tpgm::atanD): 7 operations per tangent for 16
+// (tests/test_cells_atan_tiny.py: bit for bit on 10^6 random patterns, every power of two below 2^-14 and the last 10^5 doubles below it).
+// rare: some x outside [+0, 2^-14), as ONE unsigned compare of the high word (2^-14 = 0x3F10000000000000 has a zero low word; a set sign
+// bit, a NaN or an Inf make the word large) -> caller uses atan_small_b<N, true>, and its fallback behind that.
+template <int N> TPG_DEV bool atan_tiny_b(const double (&x)[N], double (&out)[N])
+{
+    double z[N], w[N], s2[N];
+    bool rare = false;
+    TPG_UNROLL for (int e = 0; e < N; ++e) rare |= !((unsigned)__double2hiint(x[e]) < 0x3F100000u);
+    TPG_UNROLL for (int e = 0; e < N; ++e) { z[e] = x[e] * x[e]; w[e] = z[e] * z[e]; }
+    TPG_UNROLL for (int e = 0; e < N; ++e) s2[e] = w[e] * -1.99999999998764832476e-01;
+    TPG_UNROLL for (int e = 0; e < N; ++e) {
+        const double sm = z[e] * 3.33333333333329318027e-01 + s2[e];
+        out[e] = x[e] - x[e] * sm;
+    }
+    return TPG_RARE(rare);
+}
+
 // asin(x) for |x| < 0.5.  tpgm::asinD returns x for |x| < 2^-26: x + x (p/q) with p/q ~ x^2/6
 // rounds to x there.  rare: some |x| >= 0.5 (edges longer than 60 degrees: the overwritten row
 // j = 1, toy grids) -> caller uses tpgm::asinD.

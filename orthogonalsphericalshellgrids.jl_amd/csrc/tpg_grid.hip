@@ -923,9 +923,14 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, Ti
             double tt[4], at[4];
             tt[0] = tri_tan_nr(a, b, c); tt[1] = tri_tan_nr(a, b, dd);
             tt[2] = tri_tan_nr(a, c, dd); tt[3] = tri_tan_nr(b, c, dd);
-            if (__any(tpgb::atan_small_b<4, true>(tt, at))) {           // wave-uniform fallback (large, degenerate or negative triangles)
-                tt[0] = tri_tan(a, b, c); tt[1] = tri_tan(a, b, dd); tt[2] = tri_tan(a, c, dd); tt[3] = tri_tan(b, c, dd);
-                tpgb::atan_b<4>(tt, at);
+            // three tiers, each wave-uniform: +0 <= t < 2^-14 (every cell of a grid finer than ~0.9 degrees: the short exact form); the
+            // full polynomial of before for a wave with a larger tangent (coarse grids, which run what they ran, behind one branch);
+            // and the fallback for large, degenerate or negative triangles
+            if (__any(tpgb::atan_tiny_b<4>(tt, at))) {
+                if (__any(tpgb::atan_small_b<4, true>(tt, at))) {
+                    tt[0] = tri_tan(a, b, c); tt[1] = tri_tan(a, b, dd); tt[2] = tri_tan(a, c, dd); tt[3] = tri_tan(b, c, dd);
+                    tpgb::atan_b<4>(tt, at);
+                }
             }
             // (2 t0 + 2 t1 + 2 t2 + 2 t3) / 2, summed left to right, is t0 + t1 + t2 + t3 summed left to right: doubling and halving are
             // exact and commute with every rounding (no overflow / underflow at these magnitudes) -- 5 multiplications less per quadrilateral
