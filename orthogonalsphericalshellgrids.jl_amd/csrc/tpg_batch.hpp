@@ -389,7 +389,10 @@ template <int N> TPG_DEV bool atan_tiny_b(const double (&x)[N], double (&out)[N]
 // rounds to x there.  rare: some |x| >= 0.5 (edges longer than 60 degrees: the overwritten row
 // j = 1, toy grids) -> caller uses tpgm::asinD.
 // asin_small_poly_b: the evaluation alone, for a caller that decides the domain by a test of its own (asin_sqrt_b below).
-template <int N> TPG_DEV void asin_small_poly_b(const double (&x)[N], double (&out)[N])
+// SEEDLESS = true: for |x| < 2^-8 only.  q = 1 + t (qS1 + t (qS2 + ...)) with t = x^2 < 2^-16 and qS1 = -2.40339...: the inner sum lies
+// in (-2.4034, -2.4033) (the next term is t qS2 < 2^-14.9), so q = 1 - d with 0 <= d < 2.41 * 2^-16 < 2^-14.73 after its rounding: the
+// domain of tpgm::div_near<false>, which gives the bits of div_nr there without the v_rcp_f64.  Everything else is the same operation.
+template <int N, bool SEEDLESS = false> TPG_DEV void asin_small_poly_b(const double (&x)[N], double (&out)[N])
 {
     double t[N], p[N], q[N];
     TPG_UNROLL for (int e = 0; e < N; ++e) t[e] = x[e] * x[e];
@@ -405,7 +408,7 @@ template <int N> TPG_DEV void asin_small_poly_b(const double (&x)[N], double (&o
     TPG_UNROLL for (int e = 0; e < N; ++e) p[e] = t[e] * p[e];
     // q in (0.77, 1] for t < 0.25 and |p| <= 0.05 with p = 0 or |p| >= t/7 (t = x*x of a clamped sqrt: 0 or
     // >= 1e-40 here), so the unscaled division is exact-equivalent; lanes with |x| >= 0.5 or NaN are `rare`
-    TPG_UNROLL for (int e = 0; e < N; ++e) out[e] = x[e] + x[e] * tpgm::div_nr(p[e], q[e]);
+    TPG_UNROLL for (int e = 0; e < N; ++e) out[e] = x[e] + x[e] * (SEEDLESS ? tpgm::div_near<false>(p[e], q[e]) : tpgm::div_nr(p[e], q[e]));
 }
 template <int N> TPG_DEV bool asin_small_b(const double (&x)[N], double (&out)[N])
 {
@@ -421,12 +424,26 @@ template <int N> TPG_DEV bool asin_small_b(const double (&x)[N], double (&out)[N
 // (no clamp) and that r lies in the fast domain of asin.  (Before: h == 0 with a patch of the square root, min(r, 1) as a v_min_f64 and
 // asin_small_b's own |x| < 0.5 -- every element that took the patch or the scalar asin then fails the one test now.)
 // The fallback evaluates the three as the reference has them: coincident points (pole-adjacent edges), edges longer than 60 degrees (the
-// overwritten row j = 1, toy grids), NaN.  Returns whether it ran (per lane).
-template <int N> TPG_DEV bool asin_sqrt_b(const double (&h)[N], double (&out)[N])
+// overwritten row j = 1, toy grids), NaN.
+// A tier in front of that one, wave-uniform: r < 2^-8 on every element of every lane (edges shorter than 0.447 degrees: every haversine
+// of a grid of 1/4 degree or finer away from its special rows) takes the polynomial with the seedless division of its p / q.  The compare
+// stands where r < 0.5 stood, so the main path pays nothing for it; r < 2^-8 is false for what r < 0.5 is false for (NaN from h = +-0, a
+// negative h or a NaN), and a wave with any such lane runs the code of before, test and all.  2^-8 is the largest power of two whose
+// square keeps the denominator inside div_near's domain (2^-7: d < 2.41 * 2^-14).
+// Returns whether the fallback ran (per lane).  tier, for the tests: 0 the seedless form (wave-uniform), 1 the polynomial with div_nr, 2 the
+// fallback ran as well.
+template <int N> TPG_DEV bool asin_sqrt_b(const double (&h)[N], double (&out)[N], int* tier = nullptr)
 {
     double rt[N];
+    bool far = false;
+    TPG_UNROLL for (int e = 0; e < N; ++e) { rt[e] = sqrt_nr<true>(h[e]); far |= TPG_RARE(!(rt[e] < 0x1p-8)); }
+    if (!__any(far)) {
+        asin_small_poly_b<N, true>(rt, out);
+        if (tier) *tier = 0;
+        return false;
+    }
     bool rare = false;
-    TPG_UNROLL for (int e = 0; e < N; ++e) { rt[e] = sqrt_nr<true>(h[e]); rare |= TPG_RARE(!(rt[e] < 0.5)); }
+    TPG_UNROLL for (int e = 0; e < N; ++e) rare |= TPG_RARE(!(rt[e] < 0.5));
     asin_small_poly_b<N>(rt, out);
     if (rare) {
         TPG_UNROLL for (int e = 0; e < N; ++e) {
@@ -434,7 +451,25 @@ template <int N> TPG_DEV bool asin_sqrt_b(const double (&h)[N], double (&out)[N]
             out[e] = asinD(!(r >= 1.0) ? r : 1.0);      // min(r, 1) that keeps a NaN, as the reference's
         }
     }
+    if (tier) *tier = rare ? 2 : 1;
     return rare;
+}
+
+// a / b elementwise for denominators b = (1 - d) / c, c = 1 or 1/4 (QUARTER), through tpgm::div_near: the bits of div_nr without its
+// v_rcp_f64.  The tile kernel's form for the four triangle denominators D = 1 + a.b + b.c + a.c of a quadrilateral, which are 4 (1 - d)
+// with d ~ (sum of the three squared edge angles) / 8: 1.5e-6 at 1/10 degree, 1e-5 at 1/4 degree.
+// rare: some element outside +0 <= d < 2^-16, read from the high words of the exact d = near_e(b) that the division starts from: the
+// unsigned maximum of the N words against 0x3EF00000 (2^-16 has a zero low word) -- one v_max3_u32, one v_max_u32 and one compare for
+// N = 4.  A NaN, an Inf or a b far from 1 / c make the word large, and so does every set sign bit: D exceeds 4 only by the rounding of a
+// triangle whose three points all but coincide (d < 1e-16: edges below 3e-8 rad), which no ordinary cell has, so d < 0 is left to the
+// caller's other form instead of paying for |d|; d = -0 does not occur (1 - 1 = +0).  -> caller uses div_nr.
+template <int N, bool QUARTER> TPG_DEV bool div_near_b(const double (&a)[N], const double (&b)[N], double (&out)[N])
+{
+    const double c = tpgm::near_c<QUARTER>();
+    unsigned m = 0u;
+    TPG_UNROLL for (int e = 0; e < N; ++e) { const unsigned w = (unsigned)__double2hiint(tpgm::near_e(b[e], c)); m = w > m ? w : m; }
+    TPG_UNROLL for (int e = 0; e < N; ++e) out[e] = tpgm::div_near(a[e], b[e], c);
+    return TPG_RARE(!(m < 0x3EF00000u));
 }
 
 // sind / cosd pairs for |x| < 360 (longitudes in [0,360), latitudes in [-90,90]: rem(x,360) = x)

@@ -266,10 +266,9 @@ __device__ __forceinline__ double quad_area(V3 a, V3 b, V3 c, V3 d)
 // 1 + a.b + b.c + a.c of unit vectors is 0 or at least ~1e-16 in magnitude and at most 4; a zero gives
 // NaN here (rcp(0) = inf), which the callers' atan_small_b reports as `rare`, and their fallback
 // recomputes the four tangents with IEEE `/` (tri_tan).
-__device__ __forceinline__ double tri_tan_nr(V3 a, V3 b, V3 c)
-{
-    return div_nr(absD(dot3(a, cross3(b, c))), 1 + dot3(a, b) + dot3(b, c) + dot3(a, c));
-}
+__device__ __forceinline__ double tri_num(V3 a, V3 b, V3 c) { return absD(dot3(a, cross3(b, c))); }
+__device__ __forceinline__ double tri_den(V3 a, V3 b, V3 c) { return 1 + dot3(a, b) + dot3(b, c) + dot3(a, c); }
+__device__ __forceinline__ double tri_tan_nr(V3 a, V3 b, V3 c) { return div_nr(tri_num(a, b, c), tri_den(a, b, c)); }
 __device__ __forceinline__ double tri_tan(V3 a, V3 b, V3 c)
 {
     return absD(dot3(a, cross3(b, c))) / (1 + dot3(a, b) + dot3(b, c) + dot3(a, c));
@@ -921,8 +920,16 @@ __global__ __launch_bounds__(64 * R, 4) void k_cells_tile(GridK g, OutPtrs o, Ti
                 dd = V3{ rd(bW, L_CC + 3, 1), rd(bW, L_CC + 4, 1), rd(bW, L_CC + 5, 1) };
             }
             double tt[4], at[4];
-            tt[0] = tri_tan_nr(a, b, c); tt[1] = tri_tan_nr(a, b, dd);
-            tt[2] = tri_tan_nr(a, c, dd); tt[3] = tri_tan_nr(b, c, dd);
+            // the four denominators of a cell finer than ~0.3 degrees are 4 (1 - d), 0 <= d < 2^-16: the division that starts from 1/4
+            // instead of v_rcp_f64 (same bits); a wave with any other denominator divides as before (wave-uniform, like the atan tiers)
+            {
+                const double tn[4] = { tri_num(a, b, c), tri_num(a, b, dd), tri_num(a, c, dd), tri_num(b, c, dd) };
+                const double td[4] = { tri_den(a, b, c), tri_den(a, b, dd), tri_den(a, c, dd), tri_den(b, c, dd) };
+                if (__any(tpgb::div_near_b<4, true>(tn, td, tt))) {
+                    tt[0] = tri_tan_nr(a, b, c); tt[1] = tri_tan_nr(a, b, dd);
+                    tt[2] = tri_tan_nr(a, c, dd); tt[3] = tri_tan_nr(b, c, dd);
+                }
+            }
             // three tiers, each wave-uniform: +0 <= t < 2^-14 (every cell of a grid finer than ~0.9 degrees: the short exact form); the
             // full polynomial of before for a wave with a larger tangent (coarse grids, which run what they ran, behind one branch);
             // and the fallback for large, degenerate or negative triangles

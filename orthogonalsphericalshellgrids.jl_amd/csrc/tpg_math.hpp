@@ -62,6 +62,51 @@ TPG_DEV double div_nr(double a, double b)
     e = fmaD(-b, q, a);
     return fmaD(e, r, q);
 }
+// a / b for a denominator next to a known constant: b = (1 - d) / c with c = 1 (QUARTER = false) or c = 1/4 (QUARTER = true) and
+// |d| < 2^-14.  div_nr from its first `e` onward with r = c in the place of v_rcp_f64(b): the same seven operations, no seed instruction
+// (which costs 3.3-3.4 plain Float64 instructions, profiles/HISTORY.md).  near_e is that first e, which a caller's tier test reads.
+//   e0 = fma(-b, c, 1) = 1 - b c = d EXACTLY: b c is b scaled by a power of two, it lies within [1 - 2^-14, 1 + 2^-14], and the
+//        difference of two doubles within a factor of two of each other is a double (Sterbenz); the fma rounds once, to that double.
+//   r1 = fma(c, e0, c) = RN(c (1 + d)).  1 / b = c / (1 - d) = c (1 + d) / (1 - d^2), so r1 = (1 - d^2)(1 + p1) / b, |p1| <= 2^-53:
+//        relative error e1 = 1 - b r1 with |e1| <= d^2 + 2^-53 < 2^-27.99.
+//   e  = fma(-b, r1, 1) = RN(e1) (relative rounding error 2^-53 of a number below 2^-27.99: below 2^-81 absolute);
+//   r2 = fma(r1, e, r1) = RN(r1 (1 + e)) = (1 - e1^2)(1 + p2) / b up to that 2^-81: r2 = (1 + n) / b with
+//        |n| <= 2^-53 + e1^2 + 2^-80 and e1^2 <= (d^2 + 2^-53)^2 < d^4 + 2^-79.
+//        |d| < 2^-14: d^4 < 2^-56, an eighth of r2's own rounding error 2^-53 (the factor atan_tiny_b keeps as well).  2^-13 would leave
+//        2^-52, twice the rounding error: 2^-14 is the largest power of two with a margin at all.  The two callers stay further inside:
+//        the triangle denominators test |d| < 2^-16 (d^4 < 2^-64, a margin of 2^11) and the asin tail has |d| < 2.41 * 2^-16 < 2^-14.73
+//        (d^4 < 2^-58.9, a margin of 2^5.9).
+//   q0 = RN(a r2);  e2 = fma(-b, q0, a) = a - b q0 EXACTLY (the residual of a quotient that is within an ulp of a / b is a double);
+//   q  = RN(q0 + e2 r2) = RN(a / b + (e2 / b) n): the last step adds the exact residual over b, whatever q0 was, so it depends on the
+//        seed only through n, and |e2 / b| <= ulp(q0) puts the value that is rounded within |n| ulp -- 2^-52.8 of an ulp -- of a / b.
+//        That is the state div_nr reaches from the hardware seed (its r carries the same half ulp of its last rounding), and like div_nr
+//        the form is HELD to the bits of IEEE a / b on its range by test, not proved correctly rounded for every pair: a / b would have
+//        to lie within 2^-52.8 ulp of a rounding boundary to differ.  tests/test_cells_seedless_div.py: 10^7 random pairs per form over
+//        the whole of |d| < 2^-14, every power of two of d with its neighbours, the last 10^5 doubles below the threshold, b = 1 / c and
+//        its neighbours, a = +0, against IEEE `/` and against div_nr; on the device against div_nr through the math probe.
+// a: as for div_nr (a = +0, or a / b comfortably normal; a = -0 gives +0 through both: e2 = (+0) + (-0) = +0).  NaN and Inf propagate as through div_nr, but no caller sends them here.
+// near_c: the constant c.  1/4 is no inline constant of the Float64 instructions and would be built in a vector register pair at every
+// use (two v_mov_b32 per division); pinned to a scalar pair once per caller, the fma reads it as its one scalar operand (cf. tpgb::kc).
+template <bool QUARTER> TPG_DEV double near_c()
+{
+    double c = QUARTER ? 0.25 : 1.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (QUARTER) asm("" : "+s"(c));
+#endif
+    return c;
+}
+TPG_DEV double near_e(double b, double c) { return fmaD(-b, c, 1.0); }
+TPG_DEV double div_near(double a, double b, double c)
+{
+    double e = near_e(b, c);
+    double r = fmaD(c, e, c);
+    e = fmaD(-b, r, 1.0);
+    r = fmaD(r, e, r);
+    const double q = a * r;
+    e = fmaD(-b, q, a);
+    return fmaD(e, r, q);
+}
+template <bool QUARTER> TPG_DEV double div_near(double a, double b) { return div_near(a, b, near_c<QUARTER>()); }
 // NONZERO = true: the caller guarantees x > 0 (no select for the zero case)
 template <bool NONZERO = false> TPG_DEV double sqrt_nr(double x)
 {

@@ -15,7 +15,8 @@ enum { F_SIN, F_COS, F_SIND, F_COSD, F_TAND, F_ATAN, F_ASIN, F_ASINH, F_SINH, F_
        F_SQRT_NR = 20, F_DIV_NR = 21,                                                          // unscaled sqrt / division
        B_SIN_SMALL = 100, B_COS, B_ATAN, B_ATAN_TAB, B_ATAN_SMALL, B_ASIN_SMALL, B_SIND, B_COSD,      // batch
        B_SIND_LAT, B_COSD_LAT, B_COS_LAT,                                                              // latitude-domain batch forms
-       B_ATAN_TINY };                                                                                  // the tile kernel's first atan tier
+       B_ATAN_TINY,                                                                                    // the tile kernel's first atan tier
+       B_DIV_NEAR1, B_DIV_NEAR4 };                                         // seedless divisions by b ~ 1 and b ~ 4: pairs (a, b), as F_DIV_NR
 
 __global__ __launch_bounds__(256) void k_probe(int which, const double* __restrict__ x, double* __restrict__ y,
                                                int* __restrict__ rare, long long n)
@@ -44,6 +45,13 @@ __global__ __launch_bounds__(256) void k_probe(int which, const double* __restri
         case B_COSD_LAT:   r = tpgb::sincosd_lat_b<4>(a, o2, o); break;
         case B_COS_LAT:    r = tpgb::cos_lat_b<4>(a, o); break;
         case B_ATAN_TINY:  r = tpgb::atan_tiny_b<4>(a, o); break;
+        case B_DIV_NEAR1: case B_DIV_NEAR4: {                                // (a0, b0, a1, b1): both slots of a pair get a / b
+            const double n2[2] = { a[0], a[2] }, d2[2] = { a[1], a[3] };
+            double q2[2];
+            r = which == B_DIV_NEAR1 ? tpgb::div_near_b<2, false>(n2, d2, q2) : tpgb::div_near_b<2, true>(n2, d2, q2);
+            o[0] = o[1] = q2[0]; o[2] = o[3] = q2[1];
+            break;
+        }
         default: return;
         }
         for (int e = 0; e < 4; ++e) if (base + e < n) { y[base + e] = o[e]; rare[base + e] = r ? 1 : 0; }
