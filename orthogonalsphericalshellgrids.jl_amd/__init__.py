@@ -40,5 +40,7 @@ from .weno import (WENO, Centered, FluxFormAdvection, WenoTracerAdvectionPlan, w
 from .weno_momentum import (DefaultStencil, EnergyConserving, EnstrophyConserving, VectorInvariant, VelocityStencil, WenoMomentumAdvectionPlan,
                             WENOVectorInvariant, weno_momentum_advection_plan, weno_momentum_advection_tendency)
 from .weno_xyz import WenoXyzTracerAdvectionPlan, weno_xyz_tracer_advection_plan, weno_xyz_tracer_advection_tendency
+from .weno_vi import (OnlySelfUpwinding, WenoViMomentumAdvectionPlan, weno_vi_momentum_advection_plan,
+                      weno_vi_momentum_advection_tendency)
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

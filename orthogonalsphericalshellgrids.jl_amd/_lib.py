@@ -1,13 +1,13 @@
 """ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
 (include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency libraries (_advection.h,
-_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h).
+_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
 status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep,
-advection, momentum, weno, weno_momentum and weno_xyz.
+advection, momentum, weno, weno_momentum, weno_xyz and weno_vi.
 """
 import ctypes as C
 import os
@@ -185,6 +185,13 @@ WENO_XYZ_SIGNATURES = {
     "tpg_weno_xyz_tracer_advection_tendency": (_i, [C.POINTER(_vp)] * 2 + [_i] + [_vp] * 8 + [C.c_double] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_weno_vi.h declares (libtripolar_hip_weno_vi.so: the twelfth library, no test build)
+WENO_VI_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno_vi.so")
+WENO_VI_SIGNATURES = {
+    "tpg_weno_vi_last_error": (C.c_char_p, []),
+    "tpg_weno_vi_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
+}
+
 
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
@@ -240,6 +247,8 @@ weno_momentum_lib, check_weno_momentum = _library("_weno_momentum", "WENO_MOMENT
 MOMENTUM_TENDENCY_LIBRARIES = (momentum_lib, weno_momentum_lib)          # the two vorticity schemes of the velocity tendencies
 weno_xyz_lib, check_weno_xyz = _library("_weno_xyz", "WENO_XYZ_LIB_PATH", WENO_XYZ_SIGNATURES, "tpg_weno_xyz_last_error")
 WENO_TRACER_LIBRARIES = (weno_lib, weno_xyz_lib)                         # the two WENO schemes of the tracer tendency: centred in z, WENO in z
+# upwinding in every term of the velocity tendency.  Not in MOMENTUM_TENDENCY_LIBRARIES: its call takes dz_c where those two take dz_f
+weno_vi_lib, check_weno_vi = _library("_weno_vi", "WENO_VI_LIB_PATH", WENO_VI_SIGNATURES, "tpg_weno_vi_last_error")
 
 
 def ft_of(dtype):

@@ -1,5 +1,5 @@
 // tpg_momentum_tendency.hpp -- the host side that the vector-invariant momentum tendencies share (tpg_momentum.hip: enstrophy-conserving;
-// tpg_weno_momentum.hip: WENO5-upwinded vorticity term; each is a library of its own): the argument record of a call with its checks, the
+// tpg_weno_momentum.hip: WENO5-upwinded vorticity term; tpg_weno_vi.hip: upwinded vertical and kinetic-energy terms too; each is a library of its own): the argument record of a call with its checks, the
 // array list for chunk_plan, the pointer struct's fill, the work-item bound, the Args fill and the dispatch.  Host code only: a kernel, its
 // Args and the pointer struct it takes stay in its file, and so do tpg::check_geom and a scheme refusal.  A further scheme of the momentum
 // tendency starts here.
@@ -8,7 +8,8 @@
 
 namespace {
 
-// the arguments of tpg_momentum_advection_tendency and tpg_weno_momentum_advection_tendency, after tpg::check_geom
+// the arguments of tpg_momentum_advection_tendency, tpg_weno_momentum_advection_tendency and tpg_weno_vi_momentum_advection_tendency, after
+// tpg::check_geom.  `dz_f` is the call's table of vertical spacings and `dz` what its messages call it (the third call passes dz_c there)
 struct MomentumCall {
     const void *u, *v, *w;
     void *Gu, *Gv;
@@ -17,6 +18,7 @@ struct MomentumCall {
     double mask_value;
     Geom g;
     int ft;
+    const char* dz = "dz_f";
 
     // the checks both calls make, in this order; the rule reads `stencil`: Hx, Hy >= hxy and Hz >= 1
     int check(int hxy, const char* stencil) const
@@ -24,7 +26,7 @@ struct MomentumCall {
         if (!u || !v || !w) { tpg::set_error("null u, v or w"); return TPG_ERR_INVALID_ARGUMENT; }
         if (!Gu || !Gv) { tpg::set_error("null Gu or Gv"); return TPG_ERR_INVALID_ARGUMENT; }
         if (!dx_fc || !dy_fc || !az_fc || !dx_cf || !dy_cf || !az_cf || !az_cc || !az_ff || !dz_f) {
-            tpg::set_error("null dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff or dz_f");
+            tpg::set_error("null dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff or %s", dz);
             return TPG_ERR_INVALID_ARGUMENT;
         }
         if (!n_fc != !n_cf) { tpg::set_error("the count planes n_fc and n_cf are given together or not at all (%s is null)", n_fc ? "n_cf" : "n_fc"); return TPG_ERR_INVALID_ARGUMENT; }
@@ -32,7 +34,7 @@ struct MomentumCall {
         if (misaligned(esz, u, v, w)) { tpg::set_error("u, v or w pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
         if (misaligned(esz, Gu, Gv)) { tpg::set_error("Gu or Gv pointer not aligned to its element type"); return TPG_ERR_INVALID_ARGUMENT; }
         if (misaligned(esz, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff, dz_f)) {
-            tpg::set_error("dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff or dz_f pointer not aligned to its element type");
+            tpg::set_error("dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff or %s pointer not aligned to its element type", dz);
             return TPG_ERR_INVALID_ARGUMENT;
         }
         if ((uintptr_t)n_fc % 4 || (uintptr_t)n_cf % 4) { tpg::set_error("count plane pointer not aligned to int32"); return TPG_ERR_INVALID_ARGUMENT; }

@@ -33,6 +33,30 @@ __device__ __forceinline__ T weno_face(T q0, T q1, T q2, T q3, T q4)
     return ((a0 * p0 + a1 * p1) + a2 * p2) / ((a0 + a1) + a2);
 }
 
+// W5F(q0..q4; t0..t4) of include/tripolar_hip_weno_vi.h (k_weno_vi_finish, tpg_weno_vi.hip), the ONE definition: R above with the smoothness
+// indicators b2, b1, b0 formed from t0..t4 and the candidates p2, p1, p0 from q0..q4 (Oceananigans' FunctionStencil).  W5F(q; q) is R(q),
+// operation for operation
+template <typename T>
+__device__ __forceinline__ T weno_face_fs(T q0, T q1, T q2, T q3, T q4, T t0, T t1, T t2, T t3, T t4)
+{
+    constexpr T K13 = T(1) / T(3), K76 = T(7) / T(6), K116 = T(11) / T(6), K56 = T(5) / T(6), K16 = T(1) / T(6);
+    constexpr T K1312 = T(13) / T(12), K310 = T(3) / T(10), K35 = T(3) / T(5), K110 = T(1) / T(10);
+    constexpr T EPS = T(1e-8);
+    const T p2 = (K13 * q0 - K76 * q1) + K116 * q2;
+    const T p1 = (K56 * q2 - K16 * q1) + K13 * q3;
+    const T p0 = (K13 * q2 + K56 * q3) - K16 * q4;
+    const T s2 = (t0 - T(2) * t1) + t2, d2 = (t0 - T(4) * t1) + T(3) * t2;
+    const T s1 = (t1 - T(2) * t2) + t3, d1 = t1 - t3;
+    const T s0 = (t2 - T(2) * t3) + t4, d0 = (T(3) * t2 - T(4) * t3) + t4;
+    const T b2 = K1312 * (s2 * s2) + T(0.25) * (d2 * d2);
+    const T b1 = K1312 * (s1 * s1) + T(0.25) * (d1 * d1);
+    const T b0 = K1312 * (s0 * s0) + T(0.25) * (d0 * d0);
+    const T tau = abs_of(b0 - b2);
+    const T r0 = tau / (b0 + EPS), r1 = tau / (b1 + EPS), r2 = tau / (b2 + EPS);
+    const T a0 = K310 * (T(1) + r0 * r0), a1 = K35 * (T(1) + r1 * r1), a2 = K110 * (T(1) + r2 * r2);
+    return ((a0 * p0 + a1 * p1) + a2 * p2) / ((a0 + a1) + a2);
+}
+
 // R3(q0, q1, q2) of include/tripolar_hip_weno_xyz.h, the face value of order three: q1 is the upwind cell, q2 the downwind one
 template <typename T>
 __device__ __forceinline__ T weno_face3(T q0, T q1, T q2)

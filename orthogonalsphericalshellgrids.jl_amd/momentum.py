@@ -55,7 +55,9 @@ class _MomentumTendencyPlan(OperatorPlan):
     halo fill of Gu and Gv.  A scheme's class (MomentumAdvectionPlan here, WenoMomentumAdvectionPlan in weno_momentum.py) supplies what
     differs: `_refuse(scheme, what)`, the smallest halo `_HALO` with the sentence `_HALO_RULE` of its refusal, the band refusal's
     `_BAND_ROWS`, `_LIBRARY` (the names in _lib of the loader and the checker, and the C function) and `_extra(scheme)`, the arguments
-    between the mask value and Nx."""
+    between the mask value and Nx.  `_SPACINGS` names the table of vertical spacings the call takes after the metric planes: dz_f (Nz + 1
+    values) unless a class says otherwise."""
+    _SPACINGS = ("_z_all_face_spacings", z_all_face_spacings)
 
     def __init__(self, u, v, w, Gu, Gv, *, scheme, mask_immersed, fill_halos, what):
         self._refuse(scheme, what)
@@ -81,7 +83,7 @@ class _MomentumTendencyPlan(OperatorPlan):
         nfc, ncf = (None, None) if counts is None else (counts["fc"], counts["cf"])
         with _on_device(device):
             metrics = [_metric(g, name, dtype, device) for name in _METRICS]
-            dz = _grid_table(g, "_z_all_face_spacings", z_all_face_spacings, dtype, device)
+            dz = _grid_table(g, *self._SPACINGS, dtype, device)
         held = [u.data, v.data, w.data, Gu.data, Gv.data, *metrics, dz, nfc, ncf]
         args = (*(_ptr(t) for t in held), 0.0, *self._extra(scheme), u.Nx, u.Ny, u.Nz, u.Hx, u.Hy, u.Hz, _lib.ft_of(dtype))
         self._set_call(function, args, check, device, held, (Gu, Gv) if fill_halos else ())

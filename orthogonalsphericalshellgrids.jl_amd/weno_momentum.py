@@ -18,15 +18,15 @@ caller's to fill first -- the rows Ny+1..Ny+3 are the Zipper's.  Only interior c
 a pole) reaches every node whose window holds it: a model masks them.  On an ImmersedBoundaryGrid the nodes k <= n_fc[i,j] of Gu and
 k <= n_cf[i,j] of Gv get 0 inside the same launch, and everything is computed unmasked.
 
-Stays out: the rest of WENOVectorInvariant -- the upwinded divergence flux, the upwinded kinetic-energy gradient and
-VelocityStencil smoothness --, WENO in z, other orders, Oceananigans' drop of the order beside the south wall and immersed nodes, latitude
+Stays out here: the upwinded divergence flux, the upwinded kinetic-energy gradient and WENO in z of WENOVectorInvariant, which are a call
+of their own (weno_vi.py).  Stays out everywhere: VelocityStencil smoothness, other orders, Oceananigans' drop of the order beside the south wall and immersed nodes, latitude
 bands, the Julia hooks.
 
 The plan form holds its tensors: calling it enqueues on torch's current stream and allocates nothing (usable inside torch.cuda.graph)."""
 from dataclasses import dataclass
 
 from .momentum import _MomentumTendencyPlan, _tendency_fields
-from .weno import WENO
+from .weno import WENO, Centered
 
 
 @dataclass(frozen=True)
@@ -50,12 +50,24 @@ class VelocityStencil:
 
 
 @dataclass(frozen=True)
+class OnlySelfUpwinding:
+    """Oceananigans' `OnlySelfUpwinding(; cross_scheme)`: in the divergence flux and the kinetic-energy gradient only the term in the
+    advected velocity's own direction is upwinded; the cross term is the symmetric value of `cross_scheme`.  A plain record."""
+    cross_scheme: object = Centered()
+
+
+@dataclass(frozen=True)
 class VectorInvariant:
-    """Oceananigans' `VectorInvariant(; vorticity_scheme, vertical_scheme, vorticity_stencil)`: a plain record.  VectorInvariant() is the
-    default, the enstrophy-conserving vorticity term of momentum_advection_plan."""
+    """Oceananigans' `VectorInvariant(; vorticity_scheme, vertical_scheme, vorticity_stencil, kinetic_energy_gradient_scheme,
+    divergence_scheme, upwinding)`: a plain record.  VectorInvariant() is the default, the enstrophy-conserving vorticity term of
+    momentum_advection_plan.  The last three are None where nothing is upwinded beside the vorticity: the centred, energy-conserving
+    vertical term and kinetic-energy gradient."""
     vorticity_scheme: object = EnstrophyConserving()
     vertical_scheme: object = EnergyConserving()
     vorticity_stencil: object = DefaultStencil()
+    kinetic_energy_gradient_scheme: object = None
+    divergence_scheme: object = None
+    upwinding: object = None
 
 
 BUILT = VectorInvariant(vorticity_scheme=WENO(order=5), vertical_scheme=EnergyConserving(), vorticity_stencil=DefaultStencil())
@@ -66,7 +78,8 @@ def WENOVectorInvariant(vorticity_order=5):
     """The reference drivers' `WENOVectorInvariant(vorticity_order = 5)`.  Not built: always raises, naming what is."""
     raise NotImplementedError(
         f"WENOVectorInvariant(vorticity_order={vorticity_order!r}) is not built: beside the WENO vorticity term it has the upwinded divergence "
-        f"flux, the upwinded kinetic-energy gradient and VelocityStencil smoothness, and those three are missing.  Its vorticity term is "
+        f"flux, the upwinded kinetic-energy gradient and VelocityStencil smoothness.  The first two are built with DefaultStencil smoothness as "
+        f"weno_vi.BUILT (weno_vi_momentum_advection_plan); VelocityStencil smoothness is missing.  Its vorticity term alone is "
         f"built as {_BUILT_NAME}: pass that (weno_momentum.BUILT, the default)")
 
 
@@ -79,6 +92,9 @@ def _refuse(scheme, what):
             raise NotImplementedError(f"{what}: WENO of order {scheme.vorticity_scheme.order} is not built ({_BUILT_NAME} is: order 5 only)")
         if isinstance(scheme.vorticity_stencil, VelocityStencil):
             raise NotImplementedError(f"{what}: VelocityStencil smoothness is not built ({_BUILT_NAME} is: DefaultStencil only)")
+        if any(x is not None for x in (scheme.kinetic_energy_gradient_scheme, scheme.divergence_scheme, scheme.upwinding)):
+            raise NotImplementedError(f"{what}: momentum advection scheme {scheme!r} is not built here: the upwinded divergence flux and "
+                                      f"kinetic-energy gradient are weno_vi_momentum_advection_plan's; this call builds {_BUILT_NAME}")
     if not isinstance(scheme, VectorInvariant) or scheme != BUILT:
         raise NotImplementedError(f"{what}: momentum advection scheme {scheme!r} is not built ({_BUILT_NAME} is)")
 
