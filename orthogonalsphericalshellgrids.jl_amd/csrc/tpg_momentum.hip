@@ -76,28 +76,11 @@ template <typename T> constexpr int LOOKAHEAD = sizeof(T) == 8 ? TPG_MOM_LOOKAHE
 constexpr bool NT = TPG_MOM_NT;            // Gu, Gv go out in streaming stores
 constexpr int WAVES = TPG_MOM_WAVES;       // waves per SIMD the register allocation must leave room for (2: at most 256 VGPRs)
 
-struct MomPtrs {
-    const void *u, *v, *w;
-    void *Gu, *Gv;
-    const void *dxfc, *dyfc, *azfc, *dxcf, *dycf, *azcf, *azcc, *azff, *dz;
-    const int32_t *nfc, *ncf;
-};
-
-struct MomArgs {
-    int Nx, Ny, Nz, sx;
-    int cpr;                               // chunks per interior row
-    int items;                             // row tiles x cpr
-    long long plane;                       // sx * sy
-    long long off2;                        // sx * Hy + Hx: the first interior cell of a padded plane
-    long long off3;                        // plane * Hz + off2
-    double value;                          // the mask value (a T value held in a double)
-};
-
 // Arrays of the tile are indexed [r + 1][c + 1] where a row r = -1 or a column c = -1 is read, [r][c] otherwise: r = -1 is the row south
 // of the tile, r = JT the row north of it, c = -1 the column west of the chunk, c = W the column east of it.  Entries the rule does not
 // read are never loaded and never used.
 template <typename T, int W, bool GEN, bool MASK, int JT, int LA>
-__global__ __launch_bounds__(256, WAVES) void k_momentum_advection(MomPtrs p, MomArgs a)
+__global__ __launch_bounds__(256, WAVES) void k_momentum_advection(MomentumPtrs p, MomentumArgs a)
 {
     typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
@@ -348,7 +331,7 @@ int tpg_momentum_advection_tendency(const void* u, const void* v, const void* w,
     const MomentumCall call{ u, v, w, Gu, Gv, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff, dz_f, n_fc, n_cf, mask_value,
                              tpg::make_geom(Nx, Ny, Nz, Hx, Hy, Hz), ft };
     if (int rc = call.check(1, "u, v[i-1..i+1, j-1..j+1, k-1..k+1] and w[i-1, j], w[i, j-1]")) return rc;
-    return call.launch<MomPtrs, MomArgs>(ROWS<double>, ROWS<float>, "k_momentum_advection", stream, [](auto ty, auto cw, auto gen, auto mask) {
+    return call.launch(ROWS<double>, ROWS<float>, "k_momentum_advection", stream, [](auto ty, auto cw, auto gen, auto mask) {
         typedef decltype(ty) T;
         return k_momentum_advection<T, decltype(cw)::value, decltype(gen)::value, decltype(mask)::value, ROWS<T>, LOOKAHEAD<T>>;
     });

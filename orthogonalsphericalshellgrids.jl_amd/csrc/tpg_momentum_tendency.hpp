@@ -1,12 +1,31 @@
-// tpg_momentum_tendency.hpp -- the host side that the vector-invariant momentum tendencies share (tpg_momentum.hip: enstrophy-conserving;
-// tpg_weno_momentum.hip: WENO5-upwinded vorticity term; tpg_weno_vi.hip: upwinded vertical and kinetic-energy terms too; each is a library of its own): the argument record of a call with its checks, the
-// array list for chunk_plan, the pointer struct's fill, the work-item bound, the Args fill and the dispatch.  Host code only: a kernel, its
-// Args and the pointer struct it takes stay in its file, and so do tpg::check_geom and a scheme refusal.  A further scheme of the momentum
-// tendency starts here.
+// tpg_momentum_tendency.hpp -- what the vector-invariant momentum tendencies share (tpg_momentum.hip: enstrophy-conserving;
+// tpg_weno_momentum.hip: WENO5-upwinded vorticity term; tpg_weno_vi.hip: upwinded vertical and kinetic-energy terms too; each is a library of
+// its own): the pointer struct and the Args every momentum kernel takes (MomentumPtrs, MomentumArgs), and on the host side the argument
+// record of a call with its checks, the array list for chunk_plan, the pointer struct's fill, the work-item bound, the Args fill and the
+// dispatch.  No device code: a kernel stays in its file (the WENO5 vorticity kernel in tpg_weno_vorticity_kernel.hpp, which two of the
+// files include), and so do tpg::check_geom and a scheme refusal.  A further scheme of the momentum tendency starts here.
 #pragma once
 #include "tpg_operator.hpp"
 
 namespace {
+
+// what every momentum kernel is launched with
+struct MomentumPtrs {
+    const void *u, *v, *w;
+    void *Gu, *Gv;
+    const void *dxfc, *dyfc, *azfc, *dxcf, *dycf, *azcf, *azcc, *azff, *dz;
+    const int32_t *nfc, *ncf;
+};
+
+struct MomentumArgs {
+    int Nx, Ny, Nz, sx;
+    int cpr;                               // chunks per interior row
+    int items;                             // row tiles x cpr
+    long long plane;                       // sx * sy
+    long long off2;                        // sx * Hy + Hx: the first interior cell of a padded plane
+    long long off3;                        // plane * Hz + off2
+    double value;                          // the mask value (a T value held in a double)
+};
 
 // the arguments of tpg_momentum_advection_tendency, tpg_weno_momentum_advection_tendency and tpg_weno_vi_momentum_advection_tendency, after
 // tpg::check_geom.  `dz_f` is the call's table of vertical spacings and `dz` what its messages call it (the third call passes dz_c there)
@@ -65,20 +84,17 @@ struct MomentumCall {
         return na;
     }
 
-    // the pointer struct of a file's kernel (MomPtrs, WmomPtrs: the same fields)
-    template <typename P>
-    P pointers() const { return P{ u, v, w, Gu, Gv, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff, dz_f, n_fc, n_cf }; }
+    MomentumPtrs pointers() const { return MomentumPtrs{ u, v, w, Gu, Gv, dx_fc, dy_fc, az_fc, dx_cf, dy_cf, az_cf, az_cc, az_ff, dz_f, n_fc, n_cf }; }
 
-    // ONE launch of a file's kernel over (row tile, chunk) items, 256 to a block, with the file's pointer struct P and Args A (MomArgs,
-    // WmomArgs: the same fields) and its rows per item in Float64 and Float32.  kernel_of(T(), integral_constant<int, W>, bool_constant<GEN>,
-    // bool_constant<MASK>) names the instantiation.
-    template <typename P, typename A, typename K>
+    // ONE launch of a file's kernel over (row tile, chunk) items, 256 to a block, with its rows per item in Float64 and Float32.
+    // kernel_of(T(), integral_constant<int, W>, bool_constant<GEN>, bool_constant<MASK>) names the instantiation.
+    template <typename K>
     int launch(int rows_f64, int rows_f32, const char* name, void* stream, K&& kernel_of) const
     {
         const int JT = ft == TPG_F64 ? rows_f64 : rows_f32;
         const long long tiles = (g.Ny + JT - 1) / JT;
         if (tiles * (g.Nx / 2) >= (1ll << 31) - 256) { tpg::set_error("momentum advection: too many work items for 32-bit indexing"); return TPG_ERR_UNSUPPORTED; }
-        const P p = pointers<P>();
+        const MomentumPtrs p = pointers();
         void* all[13];
         const int na = arrays(all);
         hipStream_t st = tpg::as_stream(stream);
@@ -86,11 +102,11 @@ struct MomentumCall {
             typedef decltype(ty) T;
             const ChunkPlan cp = chunk_plan<T>(g, all, na);
             const int cpr = g.Nx / cp.W;
-            const A a{ g.Nx, g.Ny, g.Nz, g.sx, cpr, (int)(tiles * cpr), g.plane, interior2(g), interior3(g), n_fc ? (double)(T)mask_value : 0.0 };
+            const MomentumArgs a{ g.Nx, g.Ny, g.Nz, g.sx, cpr, (int)(tiles * cpr), g.plane, interior2(g), interior3(g), n_fc ? (double)(T)mask_value : 0.0 };
             const unsigned blocks = (unsigned)((a.items + 255) / 256);
             dispatch_chunk<T>(cp.W, cp.gen, [&](auto cw, auto gen) {
                 auto go = [&](auto mask) {
-                    void (*const kernel)(P, A) = kernel_of(ty, cw, gen, mask);
+                    void (*const kernel)(MomentumPtrs, MomentumArgs) = kernel_of(ty, cw, gen, mask);
                     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, p, a);
                 };
                 if (n_fc) go(std::true_type{});

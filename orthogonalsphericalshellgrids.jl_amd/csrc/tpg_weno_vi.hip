@@ -11,11 +11,9 @@
 // one correctly rounded IEEE operation.  Hx, Hy >= 3, Hz >= 1; only interior cells of Gu, Gv are written.
 //
 // TWO launches on the caller's stream, the split form (profiles/weno_vi/README.md has the register figures behind the choice):
-// 1. k_weno_vi_vorticity leaves hu in Gu and hv in Gv.  It is the vorticity half of k_weno_momentum_advection (tpg_weno_momentum.hip), the
-//    same item shape and the same sharing of Z: an item is ONE chunk of W columns x 2 rows and walks all levels; it keeps the cells of
-//    dx_fc, dy_cf, az_ff, dx_cf and dy_fc its nodes read in registers; it forms Z once on its own columns at the rows -2 .. JT + 2 and takes
-//    the Z beside its chunk from the lanes west and east of it (__shfl_up / __shfl_down), forming them itself from element loads, with the
-//    same bits, where that lane is in another wave, holds a chunk of another row tile or lies past the row's end (the periodic seam).
+// 1. k_weno_momentum_advection in its vorticity-only form (tpg_weno_vorticity_kernel.hpp, the one definition, shared with
+//    tpg_weno_momentum.hip) leaves hu in Gu and hv in Gv: 2 rows per item in both precisions, no look-ahead ring, the Z beside a chunk from
+//    the neighbouring lanes.
 // 2. k_weno_vi_finish reads hu, hv back at its own nodes and stores -((hu + vu) + bu), -((hv + vvert) + bv), masked: the order of the three
 //    additions is the rule's, so the bits are those of one evaluation.  An item is ONE chunk of W columns of ONE row and walks all levels.
 //    It loads once and keeps in registers the cells of dy_fc, dx_cf, az_cc, dx_fc, dy_cf, az_fc and az_cf its nodes read, and the counts.
@@ -34,6 +32,7 @@
 // all the arrays passed.  Element offsets are 64-bit.  No atomics, no LDS, nothing allocated, no host wait.
 #include "tpg_momentum_tendency.hpp"
 #include "tpg_weno_face.hpp"
+#include "tpg_weno_vorticity_kernel.hpp"
 #include "../../include/tripolar_hip_weno_vi.h"
 
 // compile-time switch of the A/B in profiles/weno_vi/ (make WENO_VI_TAG=_nt0 WENO_VI_FLAGS=-DTPG_WVI_NT=0)
@@ -44,189 +43,13 @@
 namespace {
 
 constexpr bool NT = TPG_WVI_NT;            // Gu, Gv go out in streaming stores
-constexpr int HALO = 3;                    // cells a window reads beyond the interior, whichever way the flow goes
-constexpr int LANES = 64;
 constexpr int VROWS = 2;                   // rows per item of the first launch
 constexpr int WIN = 5;                     // levels of the z-window carried from level to level
-
-struct WviPtrs {
-    const void *u, *v, *w;
-    void *Gu, *Gv;
-    const void *dxfc, *dyfc, *azfc, *dxcf, *dycf, *azcf, *azcc, *azff, *dz;
-    const int32_t *nfc, *ncf;
+struct VorticitySwitches {                 // of the first launch: neighbour-lane Z, ONE wave per SIMD
+    static constexpr bool SHARE = true;
+    static constexpr bool NT = TPG_WVI_NT;
+    static constexpr int WAVES = 1;
 };
-
-struct WviArgs {
-    int Nx, Ny, Nz, sx;
-    int cpr;                               // chunks per interior row
-    int items;                             // row tiles x cpr
-    long long plane;                       // sx * sy
-    long long off2;                        // sx * Hy + Hx: the first interior cell of a padded plane
-    long long off3;                        // plane * Hz + off2
-    double value;                          // the mask value (a T value held in a double)
-};
-
-// ---- launch 1: hu -> Gu, hv -> Gv ------------------------------------------------------------------------------------------------------------
-// Rows of the tile are r = -3 .. JT + 2 (r = 0 .. JT - 1 its own), columns c = -1 .. W (c = 0 .. W - 1 the chunk's); u and v are indexed
-// [r + 3][c + 1].  Entries the rule does not read are never loaded and never used.
-template <typename T, int W, bool GEN>
-__global__ __launch_bounds__(256, 1) void k_weno_vi_vorticity(WviPtrs p, WviArgs a)
-{
-    typedef Chunk<T, W, GEN> cvec_t;
-    constexpr int JT = VROWS;
-    constexpr int NR = JT + 2 * HALO;                              // rows -3 .. JT + 2
-    const int item = blockIdx.x * blockDim.x + threadIdx.x;
-    if (item >= a.items) return;
-    const int tile = item / a.cpr;
-    const int ch = item - tile * a.cpr;
-    const int e0 = ch * W;                                         // first interior column of the chunk (0-based)
-    const int j0 = tile * JT;                                      // first interior row of the tile (0-based)
-    const int nr = min(JT, a.Ny - j0);                             // rows of the tile inside the interior
-    const int lane = threadIdx.x % LANES;
-    // the lane west (east, second east) of this one holds the chunk west (east, second east) of this one, of the same row tile
-    const bool west_ok = lane > 0 && ch > 0;
-    const bool east1_ok = lane < LANES - 1 && ch < a.cpr - 1;
-    const bool east2_ok = lane < LANES - 2 && ch < a.cpr - 2;
-    const T half = T(0.5);
-
-    // row offsets inside a plane, rows -3 .. JT + 2 of the tile: the rows past the interior clamped onto the third row north of the last
-    // interior one (row j0 + nr + 2 <= Ny + 2, 0-based: inside the north halo, Hy >= 3); row j0 - 3 >= -3 is inside the south halo
-    int ro[NR];
-#pragma unroll
-    for (int r = -HALO; r < JT + HALO; ++r) ro[r + HALO] = a.sx * min(r, nr + HALO - 1);
-    auto chunk = [](const T* q) { return *reinterpret_cast<const cvec_t*>(q); };
-
-    const long long m0 = a.off2 + (long long)a.sx * j0 + e0;
-    const T* mdx = static_cast<const T*>(p.dxfc) + m0;
-    const T* mdy = static_cast<const T*>(p.dycf) + m0;
-    const T* maf = static_cast<const T*>(p.azff) + m0;
-    T dxfc[NR][W], dycf[NR][W + 1], azff[NR][W];                   // rows -3 .. JT + 2; -2 .. JT + 2, columns -1 .. W - 1; -2 .. JT + 2
-    T dxcf[JT + 1][W + 1], dyfc[JT + 1][W + 1];                    // rows 0 .. JT, columns -1 .. W - 1; rows -1 .. JT - 1, columns 0 .. W
-    {
-#pragma unroll
-        for (int r = -HALO; r < JT + HALO; ++r) {
-            const cvec_t x = chunk(mdx + ro[r + HALO]);
-#pragma unroll
-            for (int e = 0; e < W; ++e) dxfc[r + HALO][e] = x[e];
-            if (r > -HALO) {
-                const cvec_t y = chunk(mdy + ro[r + HALO]), f = chunk(maf + ro[r + HALO]);
-                dycf[r + HALO][0] = mdy[ro[r + HALO] - 1];
-#pragma unroll
-                for (int e = 0; e < W; ++e) { dycf[r + HALO][e + 1] = y[e]; azff[r + HALO][e] = f[e]; }
-            }
-        }
-        const T* px = static_cast<const T*>(p.dxcf) + m0;
-#pragma unroll
-        for (int r = 0; r <= JT; ++r) {
-            const cvec_t x = chunk(px + ro[r + HALO]);
-            dxcf[r][0] = px[ro[r + HALO] - 1];
-#pragma unroll
-            for (int e = 0; e < W; ++e) dxcf[r][e + 1] = x[e];
-        }
-        const T* qy = static_cast<const T*>(p.dyfc) + m0;
-#pragma unroll
-        for (int r = -1; r < JT; ++r) {
-            const cvec_t y = chunk(qy + ro[r + HALO]);
-            dyfc[r + 1][W] = qy[ro[r + HALO] + W];
-#pragma unroll
-            for (int e = 0; e < W; ++e) dyfc[r + 1][e] = y[e];
-        }
-    }
-
-    const long long f0 = a.off3 + (long long)a.sx * j0 + e0;
-    const T* u = static_cast<const T*>(p.u) + f0;
-    const T* v = static_cast<const T*>(p.v) + f0;
-    T* Gu = static_cast<T*>(p.Gu) + f0;
-    T* Gv = static_cast<T*>(p.Gv) + f0;
-
-    for (int k = 0; k < a.Nz; ++k) {
-        const T* uk = u + a.plane * k;
-        const T* vk = v + a.plane * k;
-        T Lu[NR][W + 2], Lv[NR][W + 2];
-#pragma unroll
-        for (int r = -HALO; r < JT + HALO; ++r) {
-            const cvec_t x = chunk(uk + ro[r + HALO]);
-#pragma unroll
-            for (int e = 0; e < W; ++e) Lu[r + HALO][e + 1] = x[e];
-            if (r > -HALO) {
-                const cvec_t y = chunk(vk + ro[r + HALO]);
-#pragma unroll
-                for (int e = 0; e < W; ++e) Lv[r + HALO][e + 1] = y[e];
-                Lv[r + HALO][0] = vk[ro[r + HALO] - 1];                         // v[i - 1, .]: rows -2 .. JT + 2
-            }
-            if (r >= -1 && r < JT) Lu[r + HALO][W + 1] = uk[ro[r + HALO] + W];  // u[i + 1, .]: rows -1 .. JT - 1
-        }
-        // Z at row r of the tile and column c of the chunk, any c in -2 .. W + 2, from element loads: the rule's operations, the same bits as
-        // the Z a neighbouring item forms on its own columns.  Reads columns c - 1 .. c: e0 - 3 .. e0 + W + 2, inside the row (Hx >= 3)
-        auto zeta_at = [&](int r, int c) -> T {
-            const long long o = (long long)ro[r + HALO] + c, os = (long long)ro[r + HALO - 1] + c;
-            return ((mdy[o] * vk[o] - mdy[o - 1] * vk[o - 1]) - (mdx[o] * uk[o] - mdx[os] * uk[os])) / maf[o];
-        };
-        // Z on the chunk's columns: rows -2 .. JT + 2, indexed [r + 2]
-        T Z[JT + 5][W];
-#pragma unroll
-        for (int r = -2; r < JT + HALO; ++r)
-#pragma unroll
-            for (int e = 0; e < W; ++e)
-                Z[r + 2][e] = ((dycf[r + HALO][e + 1] * Lv[r + HALO][e + 1] - dycf[r + HALO][e] * Lv[r + HALO][e])
-                               - (dxfc[r + HALO][e] * Lu[r + HALO][e + 1] - dxfc[r + HALO - 1][e] * Lu[r + HALO - 1][e + 1])) / azff[r + HALO][e];
-        // Z of the tile's rows on the columns -2 .. W + 2, indexed [c + 2]: the chunk's own, two from the lane to the west, three from the
-        // lane to the east (W = 2: two, and one from the lane after it) -- or, where that lane holds another chunk, formed here
-        T zx[JT][W + 5];
-#pragma unroll
-        for (int r = 0; r < JT; ++r) {
-#pragma unroll
-            for (int e = 0; e < W; ++e) zx[r][e + 2] = Z[r + 2][e];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) zx[r][q] = __shfl_up(Z[r + 2][W - 2 + q], 1);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) zx[r][W + 2 + q] = q < W ? __shfl_down(Z[r + 2][q % W], 1) : __shfl_down(Z[r + 2][q % W], 2);
-            if (!west_ok) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) zx[r][q] = zeta_at(r, q - 2);
-            }
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                if (!(q < W ? east1_ok : east2_ok)) zx[r][W + 2 + q] = zeta_at(r, W + q);
-        }
-        // P: rows 0 .. JT, columns -1 .. W - 1.  Q: rows -1 .. JT - 1, columns 0 .. W
-        T P[JT + 1][W + 1], Q[JT + 1][W + 1];
-#pragma unroll
-        for (int r = 0; r <= JT; ++r)
-#pragma unroll
-            for (int e = 0; e <= W; ++e) {
-                P[r][e] = dxcf[r][e] * Lv[r + HALO][e];
-                Q[r][e] = dyfc[r][e] * Lu[r + HALO - 1][e + 1];
-            }
-#pragma unroll
-        for (int r = 0; r < JT; ++r) {
-            cvec_t gu, gv;
-#pragma unroll
-            for (int e = 0; e < W; ++e) {
-                {
-                    const T vh = half * (half * (P[r][e] + P[r + 1][e]) + half * (P[r][e + 1] + P[r + 1][e + 1]));
-                    const T vhat = vh / dxfc[r + HALO][e];
-                    const bool pos = vhat >= T(0);                 // true for -0, false for NaN
-                    const T zr = weno_face<T>(pos ? Z[r][e] : Z[r + 5][e], pos ? Z[r + 1][e] : Z[r + 4][e], pos ? Z[r + 2][e] : Z[r + 3][e],
-                                              pos ? Z[r + 3][e] : Z[r + 2][e], pos ? Z[r + 4][e] : Z[r + 1][e]);     // Z[r + 2 + m][e]: Z[i, j + m]
-                    gu[e] = -(vhat * zr);
-                }
-                {
-                    const T uh = half * (half * (Q[r][e] + Q[r][e + 1]) + half * (Q[r + 1][e] + Q[r + 1][e + 1]));
-                    const T uhat = uh / dycf[r + HALO][e + 1];
-                    const bool pos = uhat >= T(0);
-                    const T zr = weno_face<T>(pos ? zx[r][e] : zx[r][e + 5], pos ? zx[r][e + 1] : zx[r][e + 4], pos ? zx[r][e + 2] : zx[r][e + 3],
-                                              pos ? zx[r][e + 3] : zx[r][e + 2], pos ? zx[r][e + 4] : zx[r][e + 1]);   // zx[r][e + 2 + m]: Z[i + m, j]
-                    gv[e] = uhat * zr;
-                }
-            }
-            if (r < nr) {
-                store_chunk<NT>(reinterpret_cast<cvec_t*>(Gu + a.plane * k + a.sx * r), gu);
-                store_chunk<NT>(reinterpret_cast<cvec_t*>(Gv + a.plane * k + a.sx * r), gv);
-            }
-        }
-    }
-}
 
 // ---- launch 2: the upwinded vertical term and kinetic-energy gradient, and the last line ---------------------------------------------------------
 template <typename T>
@@ -255,7 +78,7 @@ __device__ __forceinline__ T z_face(int cls, T M, T x0, T x1, T x2, T x3, T x4, 
 
 // Rows are r = -3 .. +3 around the item's row, columns c = -3 .. W + 2 around its chunk (c = 0 .. W - 1 the chunk's).
 template <typename T, int W, bool GEN, bool MASK>
-__global__ __launch_bounds__(256, 1) void k_weno_vi_finish(WviPtrs p, WviArgs a)
+__global__ __launch_bounds__(256, 1) void k_weno_vi_finish(MomentumPtrs p, MomentumArgs a)
 {
     typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
@@ -526,10 +349,10 @@ int tpg_weno_vi_momentum_advection_tendency(const void* u, const void* v, const 
     if (int rc = call.check(HALO, "u, v[i-3..i+3, j-3..j+3, k-3..k+3 within 0..Nz+1] and w[i-2..i+1, j], w[i, j-2..j+1]")) return rc;
     // every check precedes any launch: the second launch has the more items (one row each), so its bound is checked before the first
     if ((long long)Ny * (Nx / 2) >= (1ll << 31) - 256) { tpg::set_error("momentum advection: too many work items for 32-bit indexing"); return TPG_ERR_UNSUPPORTED; }
-    if (int rc = call.launch<WviPtrs, WviArgs>(VROWS, VROWS, "k_weno_vi_vorticity", stream, [](auto ty, auto cw, auto gen, auto) {
-            return k_weno_vi_vorticity<decltype(ty), decltype(cw)::value, decltype(gen)::value>;
+    if (int rc = call.launch(VROWS, VROWS, "k_weno_momentum_advection (vorticity term)", stream, [](auto ty, auto cw, auto gen, auto) {
+            return k_weno_momentum_advection<decltype(ty), decltype(cw)::value, decltype(gen)::value, false, VROWS, 0, VorticitySwitches, false>;
         })) return rc;
-    return call.launch<WviPtrs, WviArgs>(1, 1, "k_weno_vi_finish", stream, [](auto ty, auto cw, auto gen, auto mask) {
+    return call.launch(1, 1, "k_weno_vi_finish", stream, [](auto ty, auto cw, auto gen, auto mask) {
         return k_weno_vi_finish<decltype(ty), decltype(cw)::value, decltype(gen)::value, decltype(mask)::value>;
     });
 }

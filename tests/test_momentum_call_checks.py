@@ -1,8 +1,10 @@
-"""The enstrophy-conserving and the WENO5 momentum tendency answer a bad call alike (no GPU): one table of fabricated calls, one per check the
-two entry points have in common, goes through tpg_momentum_advection_tendency (scheme = 0) and tpg_weno_momentum_advection_tendency, and
-status and full message must be equal.  Only the halo refusal may differ, and only in the stencil it names and the halo that stencil needs.
-Every call fails in validation, none reaches a launch; the pointers are never dereferenced.  The two Python plans are one body
-(_MomentumTendencyPlan): their refusals on host-only grid records differ in the `what` prefix alone."""
+"""The enstrophy-conserving, the WENO5 and the all-upwinded momentum tendency answer a bad call alike (no GPU): one table of fabricated calls,
+one per check the three entry points have in common, goes through tpg_momentum_advection_tendency (scheme = 0),
+tpg_weno_momentum_advection_tendency and tpg_weno_vi_momentum_advection_tendency, and status and full message must be equal -- but for the
+name of the spacing table, which the third call takes at the centres (dz_c for dz_f).  Only the halo refusal may differ otherwise, and only
+in the stencil it names and the halo that stencil needs.  Every call fails in validation, none reaches a launch; the pointers are never
+dereferenced.  The three Python plans are one body (_MomentumTendencyPlan): their refusals on host-only grid records differ in the `what`
+prefix alone."""
 import pytest
 
 from test_weno_momentum_conditions import _grid
@@ -19,9 +21,12 @@ F32, F64 = 0, 1
 CENTRED_HALO = "the rule reads u, v[i-1..i+1, j-1..j+1, k-1..k+1] and w[i-1, j], w[i, j-1]: Hx >= 1, Hy >= 1 and Hz >= 1 needed (halo ({},{},{}))"
 WENO_HALO = ("the rule reads Z[i, j-2..j+3] and Z[i-2..i+3, j], that is u, v[i-3..i+3, j-3..j+3, k-1..k+1], and w[i-1, j], w[i, j-1]: "
              "Hx >= 3, Hy >= 3 and Hz >= 1 needed (halo ({},{},{}))")
+VI_HALO = ("the rule reads u, v[i-3..i+3, j-3..j+3, k-3..k+3 within 0..Nz+1] and w[i-2..i+1, j], w[i, j-2..j+1]: "
+           "Hx >= 3, Hy >= 3 and Hz >= 1 needed (halo ({},{},{}))")
 HALO_FORMAT = "the rule reads {}: Hx >= {m}, Hy >= {m} and Hz >= 1 needed (halo ({},{},{}))"
 STENCILS = {"centred": ("u, v[i-1..i+1, j-1..j+1, k-1..k+1] and w[i-1, j], w[i, j-1]", 1),
-            "weno": ("Z[i, j-2..j+3] and Z[i-2..i+3, j], that is u, v[i-3..i+3, j-3..j+3, k-1..k+1], and w[i-1, j], w[i, j-1]", 3)}
+            "weno": ("Z[i, j-2..j+3] and Z[i-2..i+3, j], that is u, v[i-3..i+3, j-3..j+3, k-1..k+1], and w[i-1, j], w[i, j-1]", 3),
+            "weno_vi": ("u, v[i-3..i+3, j-3..j+3, k-3..k+3 within 0..Nz+1] and w[i-2..i+1, j], w[i, j-2..j+1]", 3)}
 
 
 def _cases():
@@ -55,12 +60,14 @@ def _call(kind, lib, n_fc=None, n_cf=None, geom=GEOM, ft=F64, **over):
     head = (s["u"], s["v"], s["w"], s["Gu"], s["Gv"], *(s[k] for k in METRICS), n_fc, n_cf, 0.0)
     if kind == "centred":
         return lib.tpg_momentum_advection_tendency(*head, 0, *geom, ft, None), lib.tpg_momentum_last_error().decode()
+    if kind == "weno_vi":                                          # the ninth table is dz_c here
+        return lib.tpg_weno_vi_momentum_advection_tendency(*head, *geom, ft, None), lib.tpg_weno_vi_last_error().decode()
     return lib.tpg_weno_momentum_advection_tendency(*head, *geom, ft, None), lib.tpg_weno_momentum_last_error().decode()
 
 
 @pytest.fixture(scope="module")
 def libs(osg):
-    return {"centred": osg._lib.momentum_lib(), "weno": osg._lib.weno_momentum_lib()}
+    return {"centred": osg._lib.momentum_lib(), "weno": osg._lib.weno_momentum_lib(), "weno_vi": osg._lib.weno_vi_lib()}
 
 
 def test_shared_checks_answer_alike(libs):
@@ -69,14 +76,16 @@ def test_shared_checks_answer_alike(libs):
     for what, status, message, kw in cases:
         got = {kind: _call(kind, lib, **kw) for kind, lib in libs.items()}
         assert got["centred"] == got["weno"] == (status, message), what
+        assert got["weno_vi"] == (status, message.replace("dz_f", "dz_c")), what
 
 
 @pytest.mark.parametrize("halo", [(4, 4, 0), (0, 0, 0), (2, 4, 4)])
 def test_halo_refusals_differ_in_the_stencil_only(libs, halo):
     assert _call("weno", libs["weno"], geom=GEOM[:3] + halo) == (-5, WENO_HALO.format(*halo))
+    assert _call("weno_vi", libs["weno_vi"], geom=GEOM[:3] + halo) == (-5, VI_HALO.format(*halo))
     if halo != (2, 4, 4):                                          # a halo the centred stencil has room in: not a bad call of it
         assert _call("centred", libs["centred"], geom=GEOM[:3] + halo) == (-5, CENTRED_HALO.format(*halo))
-    for kind, literal in (("centred", CENTRED_HALO), ("weno", WENO_HALO)):      # one sentence around the stencil and its minimum
+    for kind, literal in (("centred", CENTRED_HALO), ("weno", WENO_HALO), ("weno_vi", VI_HALO)):      # one sentence around the stencil and its minimum
         stencil, least = STENCILS[kind]
         assert HALO_FORMAT.format(stencil, *halo, m=least) == literal.format(*halo)
 
@@ -91,6 +100,7 @@ def test_the_two_plans_are_one_body(osg):
     import torch
     from orthogonalsphericalshellgrids.jl_amd.momentum import _MomentumTendencyPlan
     assert issubclass(osg.MomentumAdvectionPlan, _MomentumTendencyPlan) and issubclass(osg.WenoMomentumAdvectionPlan, _MomentumTendencyPlan)
+    assert issubclass(osg.WenoViMomentumAdvectionPlan, _MomentumTendencyPlan)
     assert osg.MomentumAdvectionPlan.__init__ is not osg.WenoMomentumAdvectionPlan.__init__            # each keeps its own defaults
     grid, other = _grid(osg), _grid(osg)
     u, v, w = osg.XFaceField(grid), osg.YFaceField(grid), osg.ZFaceField(grid)
@@ -119,11 +129,13 @@ def test_the_two_plans_are_one_body(osg):
     one_shot = lambda f: lambda u_, v_, w_, a, b: f(u_, v_, w_, out=(a, b))                            # noqa: E731
     forms = {"momentum_advection_plan": osg.momentum_advection_plan, "weno_momentum_advection_plan": osg.weno_momentum_advection_plan,
              "momentum_advection_tendency": one_shot(osg.momentum_advection_tendency),
-             "weno_momentum_advection_tendency": one_shot(osg.weno_momentum_advection_tendency)}
+             "weno_momentum_advection_tendency": one_shot(osg.weno_momentum_advection_tendency),
+             "weno_vi_momentum_advection_plan": osg.weno_vi_momentum_advection_plan,
+             "weno_vi_momentum_advection_tendency": one_shot(osg.weno_vi_momentum_advection_tendency)}
     for kind, message, fields in calls:
         for what, fn in forms.items():
             assert _raised(fn, *fields.values()) == (kind, f"{what}: {message}"), (what, message)
-    # out=None: one helper allocates for both one-shot calls, and only after u is known to be an XFace field
-    for what in ("momentum_advection_tendency", "weno_momentum_advection_tendency"):
+    # out=None: one helper allocates for the one-shot calls, and only after u is known to be an XFace field
+    for what in ("momentum_advection_tendency", "weno_momentum_advection_tendency", "weno_vi_momentum_advection_tendency"):
         for bad in (v, u.data):
             assert _raised(getattr(osg, what), bad, v, w) == (TypeError, f"{what}: u must be a Field at (Face, Center, Center)")

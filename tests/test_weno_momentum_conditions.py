@@ -260,11 +260,16 @@ def test_the_build_names_the_library_the_map_and_the_argcheck_tool():
     assert "tpg_weno_face.hpp" in make and "tripolar_hip_weno_momentum.h" in make
     text = open(os.path.join(csrc, "weno_momentum.map")).read()
     assert all(n in text for n in NAMES) and "local: *;" in text
-    # W5 has one definition in the tree: the shared header, included by both kernels
-    for src in ("tpg_weno.hip", "tpg_weno_momentum.hip"):
+    # W5 has one definition in the tree: the shared header, included by both kernels (the momentum kernel lives in a header of its own,
+    # which this library's file includes)
+    for src in ("tpg_weno.hip", "tpg_weno_vorticity_kernel.hpp"):
         body = open(os.path.join(csrc, src)).read()
         assert '#include "tpg_weno_face.hpp"' in body and "T weno_face(" not in body
     assert open(os.path.join(csrc, "tpg_weno_face.hpp")).read().count("T weno_face(") == 1
+    body = open(os.path.join(csrc, "tpg_weno_momentum.hip")).read()
+    assert '#include "tpg_weno_vorticity_kernel.hpp"' in body and "T weno_face(" not in body and "__global__" not in body
+    assert "tpg_weno_vorticity_kernel.hpp" in [ln for ln in make.split("\n") if ln.startswith("HDRS")][0].split()
+    assert "TPG_WVI" not in body and "TPG_WMOM" not in open(os.path.join(csrc, "tpg_weno_vorticity_kernel.hpp")).read()
     tool = open(os.path.join(ROOT, "tools", "momentum_argcheck.cpp")).read()                               # one program over both momentum calls
     assert "-Xarch_host -fsanitize=address,undefined" in tool and "int main()" in tool and "tpg_weno_momentum_advection_tendency" in tool
     assert "tpg_momentum_advection_tendency" in tool and "csrc/tpg_momentum.hip" in tool and "csrc/tpg_weno_momentum.hip" in tool

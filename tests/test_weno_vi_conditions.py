@@ -274,6 +274,16 @@ def test_the_build_names_the_library_the_map_and_the_shared_definitions():
     body = open(os.path.join(csrc, "tpg_weno_vi.hip")).read()
     assert '#include "tpg_weno_face.hpp"' in body and '#include "tpg_momentum_tendency.hpp"' in body
     assert "T weno_face" not in body and "struct MomentumCall" not in body and "atomic" not in body.replace("No atomics", "").replace("no atomics", "")
+    # the WENO5 vorticity kernel has one definition, a header both momentum files include; the pointer struct and the Args have one too
+    kernel = "tpg_weno_vorticity_kernel.hpp"
+    assert kernel in [ln for ln in make.split("\n") if ln.startswith("HDRS")][0].split()
+    sources = {n: open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".hpp"))}
+    assert all(f'#include "{kernel}"' in sources[n] for n in ("tpg_weno_momentum.hip", "tpg_weno_vi.hip"))
+    assert [n for n, text in sources.items() if "auto zeta_at" in text] == [kernel] and sources[kernel].count("auto zeta_at") == 1
+    assert "__shfl" not in body and "TPG_WMOM" not in body and "TPG_W" not in sources[kernel]
+    for struct in ("struct MomentumPtrs", "struct MomentumArgs"):
+        assert sum(text.count(struct) for text in sources.values()) == 1 and struct in sources["tpg_momentum_tendency.hpp"]
+    assert not any(old in text for old in ("MomPtrs", "WmomPtrs", "WviPtrs") for text in sources.values())
     assert "weno_vi_lib" in open(os.path.join(ROOT, "__graft_entry__.py")).read()                         # build() loads it
     import json
     diff = json.load(open(os.path.join(ROOT, "profiles", "weno_vi", "isa_diff.json")))

@@ -5,9 +5,14 @@
 OLD_DIR / NEW_DIR hold the objects of csrc/ (e.g. a copy of csrc/*.o taken at the parent commit, and csrc/ itself).  For every
 object (default: every *.o in OLD_DIR) the device code object is taken out of the .hip_fatbin section (llvm-objcopy +
 clang-offload-bundler), disassembled (llvm-objdump -d) and compared per kernel symbol, together with the kernel's descriptor metadata
-(llvm-readelf --notes: register counts, spills, LDS, scratch and kernarg size).  Prints one JSON line: per object, whether the code
-objects are byte-identical and the kernels whose disassembly or metadata differs or that exist on one side only; exit status 0 only
-if there is none of either."""
+(llvm-readelf --notes: register counts, spills, LDS, scratch and kernarg size).  Kernels are paired by symbol first.  A kernel of OLD_DIR
+whose symbol is gone is then paired by content (pair_renamed): if its disassembly and its descriptor entries both equal those of exactly
+one kernel that only NEW_DIR has, the two are one kernel under a new name (a changed template parameter or argument type) and are
+reported under `renamed`, old -> new; n identical kernels against n identical kernels pair in symbol order.  Prints one JSON line: per
+object, whether the code objects are byte-identical, the renamed pairs, the kernels whose disassembly or metadata differs, and those that
+exist on one side only (`only_old`, `only_new`: what no pairing took); exit status 0 only if nothing differs and nothing is left on one
+side.  `code_object_identical` stays a byte comparison of the whole code objects: a rename changes the symbol table, so it is false for
+an object with a renamed kernel even when nothing else moved."""
 import json
 import os
 import re
@@ -69,6 +74,28 @@ def descriptors(co):
     return {r["name"]: {k: r.get(k) for k in DESCRIPTOR} for r in recs if "name" in r}
 
 
+def pair_renamed(lines_old, lines_new, desc_old, desc_new):
+    """(renamed, only_old, only_new) for two builds' symbol -> disassembly lines and symbol -> descriptor dictionaries.  Among the symbols
+    only one build has, kernels of equal content (the same lines and the same descriptor) form a group.  A group with ONE kernel on each
+    side is a rename.  So is a group with the same number n > 1 on both sides -- instantiations that compile to the same code, such as
+    the aligned and the element-aligned form of a chunk type: they are paired in symbol order, and which twin is which cannot matter,
+    every one has a partner of equal content.  A group with unequal numbers (one old kernel and two identical candidates, a kernel
+    missing on one side) pairs nothing: its kernels stay in only_old / only_new"""
+    groups = {}
+    for side, lines, desc, other in ((0, lines_old, desc_old, lines_new), (1, lines_new, desc_new, lines_old)):
+        for k in sorted(set(lines) - set(other)):
+            key = (tuple(lines[k]), tuple(sorted((desc.get(k) or {}).items())))
+            groups.setdefault(key, ([], []))[side].append(k)
+    renamed, only_old, only_new = {}, [], []
+    for old, new in groups.values():
+        if len(old) == len(new):
+            renamed.update(zip(old, new))
+        else:
+            only_old += old
+            only_new += new
+    return dict(sorted(renamed.items())), sorted(only_old), sorted(only_new)
+
+
 def main():
     old_dir, new_dir = sys.argv[1], sys.argv[2]
     names = sys.argv[3:] or sorted(n for n in os.listdir(old_dir) if n.endswith(".o"))
@@ -85,10 +112,11 @@ def main():
             ka, kb = kernels(co_a), kernels(co_b)
             da, db = descriptors(co_a), descriptors(co_b)
             assert da and set(da) <= set(ka), "kernel metadata of " + n + " not understood"
+            renamed, only_old, only_new = pair_renamed(ka, kb, da, db)
             report[n] = {"code_object_identical": a == b, "kernels": len(ka), "descriptors": len(da),
                          "differing": sorted(k for k in ka if k in kb and ka[k] != kb[k]),
-                         "metadata_differing": sorted(k for k in set(da) | set(db) if da.get(k) != db.get(k)),
-                         "only_old": sorted(set(ka) - set(kb)), "only_new": sorted(set(kb) - set(ka))}
+                         "metadata_differing": sorted(k for k in ka if k in kb and da.get(k) != db.get(k)),
+                         "renamed": renamed, "only_old": only_old, "only_new": only_new}
     print(json.dumps(report))
     bad = ("differing", "metadata_differing", "only_old", "only_new")
     return 0 if all(not any(r.get(k) for k in bad) for r in report.values()) else 1
