@@ -76,14 +76,6 @@ template <typename T, int TG> constexpr int LOOKAHEAD = TG >= 4 ? TPG_ADV_LOOKAH
 constexpr bool NT = TPG_ADV_NT;            // G goes out in streaming stores
 constexpr int WAVES = TPG_ADV_WAVES;       // waves per SIMD the register allocation must leave room for (2: at most 256 VGPRs)
 
-struct AdvPtrs {
-    const void* c[TPG_MAX_FIELDS];
-    void* G[TPG_MAX_FIELDS];
-    const void *u, *v, *w;
-    const void *dy, *dx, *az, *dz;
-    const int32_t* ncc;
-};
-
 struct AdvArgs {
     int Nx, Ny, Nz, sx;
     int q0;                                // the launch's first tracer
@@ -96,7 +88,7 @@ struct AdvArgs {
 };
 
 template <typename T, int W, bool GEN, bool MASK, int TG, int LA>
-__global__ __launch_bounds__(256, WAVES) void k_tracer_advection(AdvPtrs p, AdvArgs a)
+__global__ __launch_bounds__(256, WAVES) void k_tracer_advection(TracerPtrs p, AdvArgs a)
 {
     typedef Chunk<T, W, GEN> cvec_t;
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
@@ -292,7 +284,7 @@ int tpg_tracer_advection_tendency(const void* const* c, void* const* G, int nfie
     const Geom& g = call.g;
     const long long tiles = (Ny + JT - 1) / JT;
     if (tiles * (Nx / 2) >= (1ll << 31) - 256) { tpg::set_error("tracer advection: too many work items for 32-bit indexing"); return TPG_ERR_UNSUPPORTED; }
-    const AdvPtrs p = call.pointers<AdvPtrs>();
+    const TracerPtrs p = call.pointers();
     void* arrays[2 * TPG_MAX_FIELDS + 6];
     const int na = call.arrays(arrays);
     hipStream_t st = tpg::as_stream(stream);

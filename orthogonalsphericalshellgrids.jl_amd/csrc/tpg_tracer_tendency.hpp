@@ -1,13 +1,25 @@
-// tpg_tracer_tendency.hpp -- the host side that the flux-form tracer tendencies share (tpg_advection.hip: centred; tpg_weno.hip: WENO5 in x
-// and y; each is a library of its own): the argument record of a call with its checks, the array list for chunk_plan, the pointer struct's
-// fill and the greedy split of the tracers into groups.  Host code only: a kernel, its Args and the pointer struct it takes stay in its file,
-// and so do tpg::check_geom, a scheme refusal and the work-item bound.  A further scheme of the tracer tendency starts here.
+// tpg_tracer_tendency.hpp -- what the flux-form tracer tendencies share (tpg_advection.hip: centred; tpg_weno.hip: WENO5 in x and y;
+// tpg_weno_xyz.hip: WENO5 in x, y and z; each is a library of its own): the pointer struct every tracer kernel takes (TracerPtrs), and on
+// the host side the argument record of a call with its checks, the array list for chunk_plan, the pointer struct's fill and the greedy
+// split of the tracers into groups.  No device code: a kernel and its Args stay in its file (the WENO5 kernel, its Args and the launch of
+// its two calls in tpg_weno_tracer_kernel.hpp, which two of the files include), and so do tpg::check_geom, a scheme refusal and the
+// centred call's work-item bound.  A further scheme of the tracer tendency starts here.
 #pragma once
 #include "tpg_operator.hpp"
 
 namespace {
 
-// the arguments of tpg_tracer_advection_tendency and tpg_weno_tracer_advection_tendency, after tpg::check_geom
+// what every tracer kernel is launched with
+struct TracerPtrs {
+    const void* c[TPG_MAX_FIELDS];
+    void* G[TPG_MAX_FIELDS];
+    const void *u, *v, *w;
+    const void *dy, *dx, *az, *dz;
+    const int32_t* ncc;
+};
+
+// the arguments of tpg_tracer_advection_tendency, tpg_weno_tracer_advection_tendency and tpg_weno_xyz_tracer_advection_tendency, after
+// tpg::check_geom
 struct TracerCall {
     const void* const* c;
     void* const* G;
@@ -18,7 +30,7 @@ struct TracerCall {
     Geom g;
     int ft;
 
-    // the checks both calls make, in this order; the rule reads `stencil` of c: Hx, Hy >= hxy and Hz >= hz
+    // the checks the three calls make, in this order; the rule reads `stencil` of c: Hx, Hy >= hxy and Hz >= hz
     int check(int hxy, int hz, const char* stencil) const
     {
         if (nfields < 1) { tpg::set_error("no tracers (nfields = %d)", nfields); return TPG_ERR_INVALID_ARGUMENT; }
@@ -86,11 +98,9 @@ struct TracerCall {
         return na;
     }
 
-    // the pointer struct of a file's kernel (AdvPtrs, WenoPtrs: the same fields)
-    template <typename P>
-    P pointers() const
+    TracerPtrs pointers() const
     {
-        P p{};
+        TracerPtrs p{};
         for (int q = 0; q < nfields; ++q) { p.c[q] = c[q]; p.G[q] = G[q]; }
         p.u = u; p.v = v; p.w = w; p.dy = dy_fc; p.dx = dx_cf; p.az = az_cc; p.dz = dz_c; p.ncc = n_cc;
         return p;

@@ -1,7 +1,7 @@
 // tpg_weno_face.hpp -- the fifth-order WENO face value, the ONE definition in the tree: R(q0..q4) of include/tripolar_hip_weno.h
-// (k_weno_tracer_advection, tpg_weno.hip) and W5(q0..q4) of include/tripolar_hip_weno_momentum.h (k_weno_momentum_advection,
+// (k_weno_tracer_advection, tpg_weno_tracer_kernel.hpp) and W5(q0..q4) of include/tripolar_hip_weno_momentum.h (k_weno_momentum_advection,
 // tpg_weno_momentum.hip), operation for operation, in the field type T with no contraction.  Beside it weno_face3, R3(q0..q2) of
-// include/tripolar_hip_weno_xyz.h, and the order table of that header's z-faces (k_weno_xyz_tracer_advection, tpg_weno_xyz.hip).
+// include/tripolar_hip_weno_xyz.h, and the order table of that header's z-faces (the ZW form of that kernel, tpg_weno_xyz.hip).
 // [recalled: uniform-grid coefficients, Jiang-Shu smoothness indicators, WENO-Z weights, eps = 1e-8; parity unpinned, like every operator here]
 #pragma once
 

@@ -20,7 +20,7 @@
 //    It carries from level to level the z-windows of u and v on its columns (five levels; the sixth arrives with the level) and FZu, FZv at
 //    the level's bottom face.  Per level: the row of u from three columns west to three east of the chunk, the rows -3 .. +2 of u on the
 //    columns 0 .. W, the mirror image of v, w at the top face two cells out, and hu, hv.  The order of a z-face is the same in every lane:
-//    a scalar branch, as in k_weno_xyz_tracer_advection.  Every DU, DV, DKU of the neighbouring chunks is formed by the item itself from
+//    a scalar branch, as in the ZW form of k_weno_tracer_advection.  Every DU, DV, DKU of the neighbouring chunks is formed by the item itself from
 //    element loads (the same bits); taking them from the neighbouring lanes is not built.
 // No load leaves the cells the header lists: the levels the z-window loads ahead of a face of reduced order are clamped onto the planes
 // 0 .. Nz + 1 and never selected.  Gu, Gv go out as streaming stores in both launches.

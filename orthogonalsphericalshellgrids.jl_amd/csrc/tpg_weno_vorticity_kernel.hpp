@@ -32,7 +32,7 @@
 //   LDS, no barrier.  Formed naively a 2 x 2 item would need 24 Z per level; this one forms 14.
 // - wave edges.  A lane whose neighbour is not in its wave, not in its row tile, or past the row's end (the periodic seam: the halo columns
 //   -2, -1 and Nx .. Nx + 2) forms those Z itself, with the same operations on element loads (zeta_at: the same bits) -- lanes 0, 62 and 63 of
-//   every wave at least.  Unlike the tracer kernel's supplier lanes (tpg_weno.hip, 63 chunks a wave), no lane is given up and no chunk lies
+//   every wave at least.  Unlike the tracer kernel's supplier lanes (tpg_weno_tracer_kernel.hpp, 63 chunks a wave), no lane is given up and no chunk lies
 //   outside the interior: a supplier chunk of W = 4 columns beside the seam would read column -5 or Nx + 4, outside a row of halo 3 or 4, while
 //   zeta_at reads exactly the cells of the rule.  The wave pays the divergent piece (at most 5 Z per row) once per level.
 // - SW::SHARE = false is the naive form in x (every item forms its five neighbour Z per row by zeta_at); profiles/weno_momentum/.

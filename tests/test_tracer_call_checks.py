@@ -1,7 +1,8 @@
-"""The centred and the WENO5 tracer tendency answer a bad call alike (no GPU): one table of fabricated calls, one per check the two entry
-points have in common, goes through tpg_tracer_advection_tendency (scheme = 0) and tpg_weno_tracer_advection_tendency, and status and full
-message must be equal.  Only the halo refusal may differ, and only in the stencil it names and the halo that stencil needs.  Every call
-fails in validation, none reaches a launch; the pointers are never dereferenced."""
+"""The centred, the WENO5 x-y and the WENO5 x-y-z tracer tendency answer a bad call alike (no GPU): one table of fabricated calls, one per
+check the three entry points have in common, goes through tpg_tracer_advection_tendency (scheme = 0), tpg_weno_tracer_advection_tendency
+and tpg_weno_xyz_tracer_advection_tendency, and status and full message must be equal.  Only the halo refusal may differ, and only in the
+stencil it names and the halo that stencil needs.  Every call fails in validation, none reaches a launch; the pointers are never
+dereferenced."""
 import ctypes as C
 
 import pytest
@@ -14,7 +15,12 @@ SHARED = dict(u=BASE, v=BASE + PARENT, w=BASE + 2 * PARENT, dy=1 << 20, dx=2 << 
 TRACER = lambda q: FAR + 3 * q * PARENT                           # noqa: E731  disjoint tracers, two parents apart
 TEND = lambda q: 2 * FAR + 3 * q * PARENT                          # noqa: E731  and their tendencies
 HALO_FORMAT = "the rule reads {}, u[i+1, j] and v[i, j+1]: Hx >= {m}, Hy >= {m} and Hz >= 1 needed (halo ({},{},{}))"
-STENCILS = {"centred": ("c[i-1..i+1, j-1..j+1, k-1..k+1]", 1), "weno": ("c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-1..k+1]", 3)}
+STENCILS = {"centred": ("c[i-1..i+1, j-1..j+1, k-1..k+1]", 1), "weno": ("c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-1..k+1]", 3),
+            "weno_xyz": ("c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-3..k+3 within 0..Nz+1]", 3)}
+WENO_HALO = ("the rule reads c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-1..k+1], u[i+1, j] and v[i, j+1]: "
+             "Hx >= 3, Hy >= 3 and Hz >= 1 needed (halo ({},{},{}))")
+WENO_XYZ_HALO = ("the rule reads c[i-3..i+3, j, k], c[i, j-3..j+3, k], c[i, j, k-3..k+3 within 0..Nz+1], u[i+1, j] and v[i, j+1]: "
+                 "Hx >= 3, Hy >= 3 and Hz >= 1 needed (halo ({},{},{}))")
 
 
 def _cases(n):
@@ -53,24 +59,33 @@ def _call(kind, lib, n, nfields=None, shared=None, n_cc=None, geom=GEOM, **table
     head = (c, G, n if nfields is None else nfields, s["u"], s["v"], s["w"], s["dy"], s["dx"], s["az"], s["dz"], n_cc, 0.0)
     if kind == "centred":
         return lib.tpg_tracer_advection_tendency(*head, 0, *geom, 1, None), lib.tpg_advection_last_error().decode()
+    if kind == "weno_xyz":
+        return lib.tpg_weno_xyz_tracer_advection_tendency(*head, *geom, 1, None), lib.tpg_weno_xyz_last_error().decode()
     return lib.tpg_weno_tracer_advection_tendency(*head, *geom, 1, None), lib.tpg_weno_last_error().decode()
 
 
 @pytest.fixture(scope="module")
 def libs(osg):
-    return {"centred": osg._lib.advection_lib(), "weno": osg._lib.weno_lib()}
+    return {"centred": osg._lib.advection_lib(), "weno": osg._lib.weno_lib(), "weno_xyz": osg._lib.weno_xyz_lib()}
 
 
 @pytest.mark.parametrize("n", [1, 2, 16])
 def test_shared_checks_answer_alike(libs, n):
     for what, status, message, kw in _cases(n):
         got = {kind: _call(kind, lib, n, **kw) for kind, lib in libs.items()}
-        assert got["centred"] == got["weno"] == (status, message), (what, n)
+        assert got["centred"] == got["weno"] == got["weno_xyz"] == (status, message), (what, n)
 
 
 @pytest.mark.parametrize("n", [1, 2, 16])
 @pytest.mark.parametrize("halo", [(4, 4, 0), (0, 0, 0)])
 def test_halo_refusals_differ_in_the_stencil_only(libs, n, halo):
+    assert set(libs) == set(STENCILS)
     for kind, lib in libs.items():
         stencil, least = STENCILS[kind]
         assert _call(kind, lib, n, geom=GEOM[:3] + halo) == (-5, HALO_FORMAT.format(stencil, *halo, m=least)), (kind, n)
+    # a halo the centred stencil has room in, and the two WENO sentences written out: one sentence around the stencil and its minimum
+    assert _call("weno", libs["weno"], n, geom=GEOM[:3] + (2, 4, 4)) == (-5, WENO_HALO.format(2, 4, 4))
+    assert _call("weno_xyz", libs["weno_xyz"], n, geom=GEOM[:3] + (2, 4, 4)) == (-5, WENO_XYZ_HALO.format(2, 4, 4))
+    for kind, literal in (("weno", WENO_HALO), ("weno_xyz", WENO_XYZ_HALO)):
+        stencil, least = STENCILS[kind]
+        assert HALO_FORMAT.format(stencil, *halo, m=least) == literal.format(*halo)

@@ -242,13 +242,19 @@ def test_missing_library_fails_loudly(osg, monkeypatch, tmp_path):
 
 def test_build_and_documents_name_the_library():
     """the Makefile builds it by the one OPERATOR_LIBRARY rule pair with WENO_TAG / WENO_FLAGS, the version script exports the two names, and
-    the argument-check program is a stand-alone one with the sanitizer build line in its header"""
+    the argument-check program is a stand-alone one with the sanitizer build line in its header, naming the sources it links"""
     from test_abi import ROOT
     mk = open(os.path.join(ROOT, "orthogonalsphericalshellgrids.jl_amd", "csrc", "Makefile")).read()
     assert "$(eval $(call OPERATOR_LIBRARY,weno,$(WENOOBJ),$(WENOLIB),$(WENO_FLAGS)))" in mk and "libtripolar_hip_weno$(WENO_TAG).so" in mk
     vs = open(os.path.join(ROOT, "orthogonalsphericalshellgrids.jl_amd", "csrc", "weno.map")).read()
     assert all(n in vs for n in NAMES) and "local: *;" in vs
-    tool = open(os.path.join(ROOT, "tools", "weno_argcheck.cpp")).read()
+    tool = open(os.path.join(ROOT, "tools", "tracer_argcheck.cpp")).read()                    # one program over the three tracer calls
     assert "int main()" in tool and "-Xarch_host -fsanitize=address,undefined" in tool
-    src = open(os.path.join(ROOT, "orthogonalsphericalshellgrids.jl_amd", "csrc", "tpg_weno.hip")).read()
+    assert "csrc/tpg_weno.hip" in tool and "tpg_weno_tracer_advection_tendency" in tool
+    # the library's file and the kernel header it includes, together
+    csrc = os.path.join(ROOT, "orthogonalsphericalshellgrids.jl_amd", "csrc")
+    hip = open(os.path.join(csrc, "tpg_weno.hip")).read()
+    assert '#include "tpg_weno_tracer_kernel.hpp"' in hip and "__global__" not in hip
+    src = hip + open(os.path.join(csrc, "tpg_weno_tracer_kernel.hpp")).read()
     assert "tpg_advection.hip\"" not in src and '#include "tpg_operator.hpp"' in src
+    assert "tpg_weno_tracer_kernel.hpp" in [ln for ln in mk.split("\n") if ln.startswith("HDRS")][0].split()

@@ -260,12 +260,15 @@ def test_the_build_names_the_library_the_map_and_the_argcheck_tool():
     assert "tpg_weno_face.hpp" in make and "tripolar_hip_weno_momentum.h" in make
     text = open(os.path.join(csrc, "weno_momentum.map")).read()
     assert all(n in text for n in NAMES) and "local: *;" in text
-    # W5 has one definition in the tree: the shared header, included by both kernels (the momentum kernel lives in a header of its own,
-    # which this library's file includes)
-    for src in ("tpg_weno.hip", "tpg_weno_vorticity_kernel.hpp"):
+    # W5 has one definition in the tree: the shared header, included by both kernels (each lives in a header of its own, which its
+    # libraries' files include)
+    for src in ("tpg_weno_tracer_kernel.hpp", "tpg_weno_vorticity_kernel.hpp"):
         body = open(os.path.join(csrc, src)).read()
         assert '#include "tpg_weno_face.hpp"' in body and "T weno_face(" not in body
     assert open(os.path.join(csrc, "tpg_weno_face.hpp")).read().count("T weno_face(") == 1
+    for src in ("tpg_weno.hip", "tpg_weno_xyz.hip"):                 # the tracer libraries' files reach it through their kernel header
+        body = open(os.path.join(csrc, src)).read()
+        assert '#include "tpg_weno_tracer_kernel.hpp"' in body and "T weno_face(" not in body
     body = open(os.path.join(csrc, "tpg_weno_momentum.hip")).read()
     assert '#include "tpg_weno_vorticity_kernel.hpp"' in body and "T weno_face(" not in body and "__global__" not in body
     assert "tpg_weno_vorticity_kernel.hpp" in [ln for ln in make.split("\n") if ln.startswith("HDRS")][0].split()

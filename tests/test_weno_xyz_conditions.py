@@ -269,9 +269,14 @@ def test_build_and_documents_name_the_library():
     assert "$(eval $(call OPERATOR_LIBRARY,weno_xyz,$(WXYZOBJ),$(WXYZLIB),$(WENO_XYZ_FLAGS)))" in mk and "libtripolar_hip_weno_xyz$(WENO_XYZ_TAG).so" in mk
     assert "$(WXYZLIB)" in mk.split("\nall:")[1].splitlines()[0] and "../libtripolar_hip_weno*.so" in mk
     assert "-ffp-contract=off" in mk
-    tool = open(os.path.join(ROOT, "tools", "weno_xyz_argcheck.cpp")).read()
+    tool = open(os.path.join(ROOT, "tools", "tracer_argcheck.cpp")).read()                    # one program over the three tracer calls
     assert "int main()" in tool and "-Xarch_host -fsanitize=address,undefined" in tool and "tpg_weno_xyz.hip" in tool
-    src = open(os.path.join(csrc, "tpg_weno_xyz.hip")).read()
+    assert "tpg_weno_xyz_tracer_advection_tendency" in tool and "csrc/tpg_advection.hip" in tool and "csrc/tpg_weno.hip" in tool
+    # the library's file and the kernel header it includes, together
+    hip = open(os.path.join(csrc, "tpg_weno_xyz.hip")).read()
+    assert '#include "tpg_weno_tracer_kernel.hpp"' in hip and "__global__" not in hip
+    assert "TPG_WXYZ" not in open(os.path.join(csrc, "tpg_weno_tracer_kernel.hpp")).read() and "TPG_WENO_" not in hip
+    src = hip + open(os.path.join(csrc, "tpg_weno_tracer_kernel.hpp")).read()
     assert '#include "tpg_tracer_tendency.hpp"' in src and '#include "tpg_weno_face.hpp"' in src and "TracerCall" in src and "check_geom" in src
     assert "weno_face3" in src and "__shared__" not in src and "atomic" not in src.replace("No atomics", "")
     face = open(os.path.join(csrc, "tpg_weno_face.hpp")).read()
