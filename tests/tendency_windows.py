@@ -1,8 +1,9 @@
-"""What tests/test_tendency_windows_ref.py (CPU) and tests/test_gpu_tendency_edges.py (GPU) share: ONE table of the six tendency kernels --
-the centred, WENO5 x/y and all-WENO tracer tendencies, the vector-invariant momentum tendency and its WENO5-upwinded form, the free-surface
-sub-step -- with each one's library, symbol, array list and numpy reference; the two cut-outs of a problem (rows, planes) with the shifted
-count planes; the levels of an all-WENO plane window that agree with the column; the whole-array comparison on integer views; and a host
-mirror of the kernels' index arithmetic (walk).
+"""What tests/test_tendency_windows_ref.py (CPU), tests/gpu_harness.py and the GPU tests of the tendencies share: ONE table of the seven
+tendency kernels -- the centred, WENO5 x/y and all-WENO tracer tendencies, the vector-invariant momentum tendency, its form with the
+WENO5-upwinded vorticity term and the one upwinded in every term, the free-surface sub-step -- with each one's library, symbol, array list
+and numpy reference; the two cut-outs of a problem (rows, planes) with the shifted count planes; the levels of an all-WENO plane window that
+agree with the column; the whole-array comparison on integer views; and a host mirror of the index arithmetic of the five 3-D kernels of
+one launch (walk; SMALLEST has their smallest shapes and the free surface's).
 
 A problem is a dict of arrays by the names of the table.  Everything here only indexes, so it works alike on numpy arrays and on torch
 tensors, on any device: the GPU tests cut the very tensors the big call ran on."""
@@ -13,6 +14,7 @@ import free_surface_ref
 import momentum_ref
 import weno_momentum_ref
 import weno_ref
+import weno_vi_ref
 import weno_xyz_ref
 from vorticity_ref import same_bits
 
@@ -59,12 +61,14 @@ def _tracer_ref(module):
     return ref
 
 
-def _momentum_ref(module):
+def _momentum_ref(module, arrays):
+    spacing = arrays["column"][0]                      # dz_f, or dz_c for the tendency upwinded in every term
+
     def ref(h, size, halo, masked):
         n = (h["n_fc"], h["n_cf"]) if masked else (None, None)
         with np.errstate(all="ignore"):
             Gu, Gv = module.tendencies(h["u"], h["v"], h["w"], _sentinel_like(h["u"]), _sentinel_like(h["u"]),
-                                       {k: h[k] for k in momentum_ref.METRICS}, h["dz_f"], size, halo, *n, MASK_VALUE)
+                                       {k: h[k] for k in momentum_ref.METRICS}, h[spacing], size, halo, *n, MASK_VALUE)
         return {"Gu": Gu, "Gv": Gv}
     return ref
 
@@ -80,6 +84,7 @@ _TRACER = dict(fields=("c", "u", "v"), tall=("w",), planes=("dy_fc", "dx_cf", "a
                counts=("n_cc",), outputs=("G",), out_rank=3)
 _MOMENTUM = dict(fields=("u", "v"), tall=("w",), planes=momentum_ref.METRICS, signed=("u", "v", "w"), column=("dz_f", 1),
                  counts=("n_fc", "n_cf"), outputs=("Gu", "Gv"), out_rank=3)
+_UPWINDED = dict(_MOMENTUM, column=("dz_c", 0))        # upwinded in every term: the spacings of the centres
 # jt: rows per work item by element size, share: the form with a chunk past the row's end -- the kernels' compile-time defaults, for walk()
 KERNELS = {k.name: k for k in (
     Kernel("advection", "advection", "tpg_tracer_advection_tendency", arm=(1, 1, 1), centred_in_z=True, scheme_arg=True, jt={8: 2, 4: 2},
@@ -89,9 +94,11 @@ KERNELS = {k.name: k for k in (
     Kernel("weno_xyz", "weno_xyz", "tpg_weno_xyz_tracer_advection_tendency", arm=(3, 3, 1), centred_in_z=False, scheme_arg=False,
            jt={8: 2, 4: 2}, share=True, ref=_tracer_ref(weno_xyz_ref), **_TRACER),
     Kernel("momentum", "momentum", "tpg_momentum_advection_tendency", arm=(1, 1, 1), centred_in_z=True, scheme_arg=True, jt={8: 1, 4: 2},
-           share=False, ref=_momentum_ref(momentum_ref), **_MOMENTUM),
+           share=False, ref=_momentum_ref(momentum_ref, _MOMENTUM), **_MOMENTUM),
     Kernel("weno_momentum", "weno_momentum", "tpg_weno_momentum_advection_tendency", arm=(3, 3, 1), centred_in_z=True, scheme_arg=False,
-           jt={8: 2, 4: 2}, share=False, ref=_momentum_ref(weno_momentum_ref), **_MOMENTUM),
+           jt={8: 2, 4: 2}, share=False, ref=_momentum_ref(weno_momentum_ref, _MOMENTUM), **_MOMENTUM),
+    Kernel("weno_vi", "weno_vi", "tpg_weno_vi_momentum_advection_tendency", arm=(3, 3, 1), centred_in_z=False, scheme_arg=False,
+           jt={8: 1, 4: 1}, share=False, ref=_momentum_ref(weno_vi_ref, _UPWINDED), **_UPWINDED),
     Kernel("free_surface", "free_surface", "tpg_free_surface_substep", fields=(), tall=(), planes=("eta", "U", "V", "GU", "GV") + free_surface_ref.METRICS,
            signed=("eta", "U", "V", "GU", "GV"), column=("depth", 1), counts=("n_fc", "n_cf"), outputs=("eta_out", "U_out", "V_out"), out_rank=2,
            arm=(1, 1, 0), centred_in_z=True, scheme_arg=False, jt={8: 2, 4: 2}, share=False, ref=_free_surface_ref))}

@@ -8,21 +8,23 @@ arm ends on the last halo cell); odd Hx (the element-aligned chunks), also with 
 twice the look-ahead and no multiple of it; an odd Ny (a partial last row tile) on Float32 rows that sit on the 16-B grid; the model halo 5; Float32 with Nx = 2 mod 4 (8-B
 chunks); one shape with more work items than are resident.  dz_c is random in [0.5, 2], so a wrong k index cannot hide."""
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
 import torch
 
 import ab2_ref
+import gpu_harness as H
+import tendency_windows as tw
 from advection_ref import cells_read, interior_tendency, same_bits, tendency
 from continuity_ref import w_and_divergence
-from immersed_ref import draw_columns, heights_of
+from gpu_harness import (F32, F64, MASK_VALUE, SENTINEL, _assert_inputs_unchanged, _assert_parent, _count_plane, _dev, _filled,  # noqa: F401
+                         _free_hbm, _id, _tracer_model as _model)
 from special_values import pool
 
 pytestmark = pytest.mark.gpu
 
-F32, F64 = np.float32, np.float64
+KERNEL = tw.KERNELS["advection"]
 #         size            halo       element type
 SMALL = [((10, 10, 1), (4, 4, 4), F64),            # one level: both vertical faces read a halo plane
          ((20, 12, 3), (1, 1, 1), F64),            # every stencil arm ends on the last halo cell
@@ -35,107 +37,30 @@ SMALL = [((10, 10, 1), (4, 4, 4), F64),            # one level: both vertical fa
          ((50, 40, 3), (4, 4, 4), F32)]            # Nx = 2 mod 4: 8-B chunks
 BIG = ((2304, 1283, 2), (4, 4, 4), F64)            # one tracer: >= 321 row tiles x 1152 chunks, more items than are resident; 1283 is odd
 OFFSET = [SMALL[3], SMALL[4], SMALL[8]]            # every pointer one element off the 16-B grid: the GEN form by the pointers, not the rows
-SENTINEL = 12345.0
-MASK_VALUE = 0.1                                   # not representable: converted once to the field type
 NTRACERS = 3
-SHARED = ("u", "v", "w", "dy_fc", "dx_cf", "az_cc", "dz_c")
 
 
-def _id(case):
-    size, halo, dtype = case
-    return "x".join(map(str, size)) + "-h" + "".join(map(str, halo)) + ("-f64" if dtype == F64 else "-f32")
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
-
-
-def _shapes(size, halo):
-    """(parent of c, G, u, v; parent of w; plane)"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    return (Nz + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Nz + 1 + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Ny + 2 * Hy, Nx + 2 * Hx)
-
-
-def _ref(h, c, size, halo, n_cc=None, value=0.0):
-    """the reference parent of G of the tracer `c` from a sentinel-filled one"""
-    with np.errstate(all="ignore"):
-        return tendency(c, h["u"], h["v"], h["w"], np.full(c.shape, SENTINEL, c.dtype), h["dy_fc"], h["dx_cf"], h["az_cc"], h["dz_c"], size, halo,
-                        n_cc, value)
-
-
-_CASES = {}
+def _ref(h, c, size, halo, n_cc=None):
+    """the reference parent of G of the tracer `c` from a sentinel-filled one; with a count plane: masked to MASK_VALUE"""
+    return H._ref(KERNEL, h, size, halo, () if n_cc is None else (n_cc,), c)
 
 
 def _case(case, ntracers=NTRACERS):
-    """host arrays of a case, random in EVERY cell (halos included), and the reference parents of G from sentinel-filled ones: computed once
-    per case, shared by the tests, never modified (tests copy what they change)"""
-    key = (case, ntracers)
-    if key not in _CASES:
-        size, halo, dtype = case
-        parent, wparent, plane = _shapes(size, halo)
-        rng = np.random.default_rng([*size, *halo, np.dtype(dtype).itemsize])
-        h = {"u": rng.uniform(-1, 1, parent).astype(dtype), "v": rng.uniform(-1, 1, parent).astype(dtype),
-             "w": rng.uniform(-1, 1, wparent).astype(dtype),
-             "dy_fc": rng.uniform(0.5, 2, plane).astype(dtype), "dx_cf": rng.uniform(0.5, 2, plane).astype(dtype),
-             "az_cc": rng.uniform(0.5, 2, plane).astype(dtype), "dz_c": rng.uniform(0.5, 2, size[2]).astype(dtype)}
-        h["c"] = [rng.uniform(-1, 1, parent).astype(dtype) for _ in range(ntracers)]
-        h["want"] = [_ref(h, c, size, halo) for c in h["c"]]
-        for a in (*h["c"], *h["want"], *(h[k] for k in SHARED)):
-            a.setflags(write=False)
-        _CASES[key] = h
-    return _CASES[key]
+    return H._case(KERNEL, case, ntracers)
 
 
 def _device(h, gpu, offset=0):
-    d = {k: _dev(h[k], gpu, offset) for k in SHARED}
-    d["c"] = [_dev(c, gpu, offset) for c in h["c"]]
-    return d
+    return H._device(KERNEL, h, gpu, offset)
 
 
 def _raw_call(osg, gpu, d, tracers, outs, size, halo, n_cc=None, value=0.0, scheme=0):
-    lib = osg._lib.advection_lib()
-    return lib.tpg_tracer_advection_tendency(
-        osg._lib.ptr_table(tracers), osg._lib.ptr_table(outs), len(tracers), d["u"].data_ptr(), d["v"].data_ptr(), d["w"].data_ptr(),
-        d["dy_fc"].data_ptr(), d["dx_cf"].data_ptr(), d["az_cc"].data_ptr(), d["dz_c"].data_ptr(), None if n_cc is None else n_cc.data_ptr(),
-        value, scheme, *size, *halo, osg._lib.ft_of(d["u"].dtype), osg._lib.current_stream_ptr(gpu))
+    return H._launch(osg, gpu, KERNEL, dict(d, c=tracers), {"G": outs}, size, halo, counts=(n_cc,), value=value, scheme=scheme)
 
 
 def _call(osg, gpu, d, size, halo, which=None, n_cc=None, value=0.0, offset=0):
     """tpg_tracer_advection_tendency on the tracers `which` (indices; None: all) of the device arrays d into fresh sentinel-filled outputs ->
     the whole parents of G on the host"""
-    tracers = d["c"] if which is None else [d["c"][q] for q in which]
-    T = {torch.float64: F64, torch.float32: F32}[d["u"].dtype]
-    outs = [_dev(np.full(tuple(t.shape), SENTINEL, T), gpu, offset) for t in tracers]
-    osg._lib.check_advection(_raw_call(osg, gpu, d, tracers, outs, size, halo, n_cc, value))
-    return [o.cpu().numpy() for o in outs]
-
-
-def _assert_parent(got, want, what):
-    bad = same_bits(got, want)
-    assert bad == 0, (what, bad, "cells differ of", got.size)
-
-
-def _assert_inputs_unchanged(d, h, what):
-    for k in SHARED:
-        _assert_parent(d[k].cpu().numpy(), h[k], (what, "input", k))
-    for q, c in enumerate(d["c"]):
-        _assert_parent(c.cpu().numpy(), h["c"][q], (what, "input tracer", q))
+    return H._call(osg, gpu, KERNEL, d, size, halo, which, (n_cc,), value, offset)
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------------------
@@ -193,7 +118,7 @@ def test_sixteen_tracers_grouped_and_one_by_one(osg, gpu, case):
     n = _count_plane(case)
     masked = _call(osg, gpu, d, size, halo, which=range(3, 10), n_cc=_dev(n, gpu), value=MASK_VALUE)
     for q, got in enumerate(masked, 3):
-        _assert_parent(got, _ref(h, h["c"][q], size, halo, n, MASK_VALUE), ("seven, masked", q))
+        _assert_parent(got, _ref(h, h["c"][q], size, halo, n), ("seven, masked", q))
     _assert_inputs_unchanged(d, h, "16 tracers")
 
 
@@ -214,26 +139,6 @@ def test_no_cell_outside_the_stencil_is_read(osg, gpu, case, offset):
         _assert_parent(got[q], h["want"][q], ("poisoned", q))
 
 
-_PLANES = {}
-
-
-def _count_plane(case):
-    """a (Center, Center) count plane for a drawn bottom (land columns, open columns, everything between) with a count above Nz and a
-    negative one planted (a count plane of a deeper grid; a column the counts call never writes).  Computed once per case."""
-    if case in _PLANES:
-        return _PLANES[case]
-    size, halo, dtype = case
-    Nx, Ny, Nz = size
-    rng = np.random.default_rng([11, *size, *halo])
-    n = draw_columns(rng, Nx, Ny, Nz).astype(np.int32)
-    n[Ny - 1, Nx - 1] = Nz + 3
-    n[0, 0] = -2
-    assert n.shape == (Ny, Nx) and (n == 0).any() and (n == Nz).any() and (Nz < 2 or ((n > 0) & (n < Nz)).any())
-    n.setflags(write=False)
-    _PLANES[case] = n
-    return n
-
-
 @pytest.mark.parametrize("case,offset", [(c, 0) for c in SMALL] + [(OFFSET[0], 1)], ids=[_id(c) for c in SMALL] + [_id(OFFSET[0]) + "-offset"])
 def test_fused_mask_equals_the_reference_and_the_mask_pass(osg, gpu, case, offset):
     """with a count plane: (1) the reference with the mask; (2) the unmasked call followed by tpg_mask_immersed_fields on G (zloc Center),
@@ -242,7 +147,7 @@ def test_fused_mask_equals_the_reference_and_the_mask_pass(osg, gpu, case, offse
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     h = _case(case)
     n = _count_plane(case)
-    want = [_ref(h, c, size, halo, n, MASK_VALUE) for c in h["c"]]
+    want = [_ref(h, c, size, halo, n) for c in h["c"]]
     inner = lambda a: a[Hz:Hz + Nz, Hy:Hy + Ny, Hx:Hx + Nx]
     assert (inner(want[0])[:, Ny - 1, Nx - 1] == dtype(MASK_VALUE)).all()                # n > Nz: the whole column
     assert same_bits(inner(want[0])[:, 0, 0], inner(h["want"][0])[:, 0, 0]) == 0         # n < 0: nothing
@@ -332,47 +237,10 @@ def test_error_returns_on_device_pointers(osg, gpu):
 DT, CHI = 0.01, 0.1
 
 
-def _np_type(tdt):
-    return F64 if tdt == torch.float64 else F32
-
-
-def _filled(osg, like, interior, base):
-    """the parent fill_halo_regions gives a field at `like`'s location and grid that held `base` (a parent) and got that interior"""
-    f = osg.Field(like.loc, like.grid)
-    f.data.copy_(torch.from_numpy(np.ascontiguousarray(base)).reshape(f.data.shape))
-    f.interior().copy_(torch.from_numpy(np.ascontiguousarray(interior)).reshape(f.interior().shape))
-    osg.fill_halo_regions([f])
-    return f.data.cpu().numpy()
-
-
-def _model(osg, gpu, size, halo, tdt, immersed, ntracers=2, seed=3):
-    """(grid, tracers, u, v, w, G, Gm): filled c, u, v, w from compute_w_from_continuity, random tendencies"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    grid = osg.TripolarGrid(osg.GPU(0), tdt, size=size, halo=halo, z=(-1, 0))
-    if immersed:
-        zc = grid.z_centers[Hz:Hz + Nz].cpu().numpy()
-        rng = np.random.default_rng(19)
-        grid = osg.ImmersedBoundaryGrid(grid, osg.GridFittedBottom(heights_of(draw_columns(rng, Nx, Ny, Nz), zc, rng)))
-    gen = torch.Generator(device=gpu).manual_seed(seed)
-    u, v = osg.XFaceField(grid), osg.YFaceField(grid)
-    tracers, G, Gm = ([osg.CenterField(grid) for _ in range(ntracers)] for _ in range(3))
-    for f in (u, v, *tracers, *G, *Gm):
-        f.data.uniform_(-1, 1, generator=gen)
-    osg.fill_halo_regions([u, v, *tracers])
-    w = osg.compute_w_from_continuity(u, v)
-    return grid, tracers, u, v, w, G, Gm
-
-
 def _host_model(osg, grid, u, v, w, size, halo):
-    """host copies of u, v, the grid's own metric arrays and spacings, and w held equal to the continuity reference's"""
+    """the harness's host model, its w held equal to the continuity reference's"""
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    g = getattr(grid, "underlying_grid", grid)
-    h = {"u": u.data.cpu().numpy(), "v": v.data.cpu().numpy(), "w": w.data.cpu().numpy()}
-    for k in ("dy_fc", "dx_cf", "az_cc"):
-        h[k] = g.arrays[k].cpu().numpy()
-    h["dz_c"] = osg.z_center_spacings(grid, u.data.dtype).numpy().astype(h["u"].dtype)
-    counts = getattr(grid, "column_counts", None)
-    h["n_cc"] = None if counts is None else counts["cc"].cpu().numpy()
+    h = H._host_model(osg, grid, u, v, w)
     want_w, _ = w_and_divergence(h["u"], h["v"], np.zeros_like(h["w"]), None, h["dy_fc"], h["dx_cf"], h["az_cc"], h["dz_c"], size, halo, h["n_cc"], 0.0)
     cut = (slice(Hz, Hz + Nz + 1), slice(Hy, Hy + Ny), slice(Hx, Hx + Nx))
     _assert_parent(h["w"][cut], want_w[cut], "w is the continuity reference's")

@@ -9,7 +9,6 @@ product); no halo at all; rows off the 16-B grid with an odd Hx and Hy2 < Hy; th
 config 5's Hy2 = 31; Float32 with Nx = 2 mod 4 (8-B chunks); one shape with more work items than are resident; and one case past 2^31
 elements.  dz_c is random in [0.5, 2] and depth_of_count random positive, so a wrong k or n index cannot hide."""
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ import torch
 import barotropic_ref as ref
 from barotropic_ref import same_bits
 from continuity_ref import interior_w_and_divergence
+from gpu_harness import _dev, _free_hbm  # noqa: F401
 from immersed_ref import draw_columns, heights_of
 from special_values import pool
 
@@ -44,26 +44,6 @@ PLANES = ("U", "V", "Ubar", "Vbar")
 def _id(case):
     size, halo, Hy2, dtype = case
     return "x".join(map(str, size)) + "-h" + "".join(map(str, halo)) + f"-{Hy2}" + ("-f64" if dtype == F64 else "-f32")
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
 
 
 def _shapes(size, halo, Hy2):

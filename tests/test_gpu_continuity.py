@@ -8,13 +8,13 @@ north read is the halo's only cell); rows off the 16-B grid with an odd Hx (the 
 Nx = 2 mod 4 (8-B chunks); one shape with more work items than resident threads and Ny a multiple of none of the row counts an item may own;
 and one case past 2^31 elements.  dz_c is random in [0.5, 2], so a wrong k index cannot hide."""
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
 import torch
 
 from continuity_ref import cells_read, interior_w_and_divergence, same_bits, w_and_divergence
+from gpu_harness import _assert_parent, _dev, _free_hbm, _id  # noqa: F401
 from immersed_ref import draw_columns, heights_of
 from special_values import pool
 
@@ -33,31 +33,6 @@ TABLE = [((10, 10, 1), (4, 4, 4), F64),            # the reference's own test si
 SENTINEL = 12345.0
 MASK_VALUE = 0.1                                   # not representable: converted once to the field type
 FORMS = {"both": (True, True), "w": (True, False), "div": (False, True)}
-
-
-def _id(case):
-    size, halo, dtype = case
-    return "x".join(map(str, size)) + "-h" + "".join(map(str, halo)) + ("-f64" if dtype == F64 else "-f32")
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
 
 
 def _shapes(size, halo):
@@ -114,11 +89,6 @@ def _call(osg, gpu, d, size, halo, form="both", n_cc=None, value=0.0, offset=0):
         d["u"].data_ptr(), d["v"].data_ptr(), ptr(w), ptr(div), d["dy_fc"].data_ptr(), d["dx_cf"].data_ptr(), d["az_cc"].data_ptr(),
         d["dz_c"].data_ptr(), ptr(n_cc), value, *size, *halo, osg._lib.ft_of(d["u"].dtype), osg._lib.current_stream_ptr(gpu)))
     return (None if w is None else w.cpu().numpy()), (None if div is None else div.cpu().numpy())
-
-
-def _assert_parent(got, want, what):
-    bad = same_bits(got, want)
-    assert bad == 0, (what, bad, "cells differ of", got.size)
 
 
 def _assert_forms(osg, gpu, d, size, halo, want_w, want_div, what, n_cc=None, value=0.0, offset=0):

@@ -9,7 +9,6 @@ an item for 2, 4 and 8 rows; below them is Ny = 1, which the call refuses); halo
 chunks) and halo 5 or 1 (element-aligned chunks); Hy2 from 1 to config 5's 31; one shape with more work items than are resident.  Every
 case runs with every pointer on the 16-B grid and one element past an allocation, with and without count planes (land columns among them),
 with and without averaging.  The metrics are random in [0.5, 2] and depth_of_count random positive, so a wrong index cannot hide."""
-import gc
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ import torch
 import barotropic_ref
 import free_surface_ref as ref
 from free_surface_ref import METRICS, same_bits
+from gpu_harness import _dev, _free_hbm  # noqa: F401
 from immersed_ref import draw_columns, heights_of
 from special_values import pool
 
@@ -44,26 +44,6 @@ PLANES = STATE + FORCING + BARS + METRICS
 def _id(case):
     size, Hx, Hy2, dtype = case
     return "x".join(map(str, size)) + f"-h{Hx}-{Hy2}" + ("-f64" if dtype == F64 else "-f32")
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
 
 
 _CASES = {}

@@ -12,20 +12,22 @@ further size: the partial tile exists in Float32 only and 24 x 11 x 5 is a Float
 look-ahead and no multiple of it (9 levels do the same for Float64, and for its measured 2-row / look-ahead-2 variants 10 rows stay whole).
 dz_f is random in [0.5, 2], so a wrong face index cannot hide."""
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
 import torch
 
 import ab2_ref
-from immersed_ref import draw_columns, heights_of
+import gpu_harness as H
+import tendency_windows as tw
+from gpu_harness import (F32, F64, MASK_VALUE, SENTINEL, _assert_inputs_unchanged, _assert_pair, _assert_parent, _count_planes, _dev,  # noqa: F401
+                         _filled, _free_hbm, _host_metrics, _id, _velocity_model as _model)
 from momentum_ref import METRICS, cells_read, same_bits, tendencies
 from special_values import pool
 
 pytestmark = pytest.mark.gpu
 
-F32, F64 = np.float32, np.float64
+KERNEL = tw.KERNELS["momentum"]
 #         size            halo       element type
 SMALL = [((10, 10, 1), (4, 4, 4), F64),            # one level: both vertical faces read a halo plane
          ((20, 12, 3), (1, 1, 1), F64),            # every stencil arm and both corners end on the last halo cell
@@ -38,103 +40,30 @@ SMALL = [((10, 10, 1), (4, 4, 4), F64),            # one level: both vertical fa
          ((50, 40, 3), (4, 4, 4), F32)]            # Nx = 2 mod 4: 8-B chunks
 BIG = ((2304, 1283, 2), (4, 4, 4), F64)            # 1283 row tiles x 1152 chunks, more items than are resident; 1283 is odd
 OFFSET = [SMALL[3], SMALL[4], SMALL[8]]            # every pointer one element off the 16-B grid: the GEN form by the pointers, not the rows
-SENTINEL = 12345.0
-MASK_VALUE = 0.1                                   # not representable: converted once to the field type
 FIELDS = ("u", "v", "w")
 SHARED = (*FIELDS, *METRICS, "dz_f")
 
 
-def _id(case):
-    size, halo, dtype = case
-    return "x".join(map(str, size)) + "-h" + "".join(map(str, halo)) + ("-f64" if dtype == F64 else "-f32")
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
-
-
-def _shapes(size, halo):
-    """(parent of u, v, Gu, Gv; parent of w; plane)"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    return (Nz + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Nz + 1 + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Ny + 2 * Hy, Nx + 2 * Hx)
-
-
-def _ref(h, size, halo, n_fc=None, n_cf=None, value=0.0):
-    """the reference parents (Gu, Gv) from sentinel-filled ones"""
-    G0 = np.full(h["u"].shape, SENTINEL, h["u"].dtype)
-    with np.errstate(all="ignore"):
-        return tendencies(h["u"], h["v"], h["w"], G0, G0, {k: h[k] for k in METRICS}, h["dz_f"], size, halo, n_fc, n_cf, value)
-
-
-_CASES = {}
+def _ref(h, size, halo, n_fc=None, n_cf=None):
+    """the reference parents (Gu, Gv) from sentinel-filled ones; with the count planes: masked to MASK_VALUE"""
+    return H._ref(KERNEL, h, size, halo, () if n_fc is None else (n_fc, n_cf))
 
 
 def _case(case):
-    """host arrays of a case, random in EVERY cell (halos included), and the reference parents of Gu, Gv from sentinel-filled ones: computed
-    once per case, shared by the tests, never modified (tests copy what they change)"""
-    if case not in _CASES:
-        size, halo, dtype = case
-        parent, wparent, plane = _shapes(size, halo)
-        rng = np.random.default_rng([*size, *halo, np.dtype(dtype).itemsize])
-        h = {"u": rng.uniform(-1, 1, parent).astype(dtype), "v": rng.uniform(-1, 1, parent).astype(dtype),
-             "w": rng.uniform(-1, 1, wparent).astype(dtype), "dz_f": rng.uniform(0.5, 2, size[2] + 1).astype(dtype)}
-        h.update({k: rng.uniform(0.5, 2, plane).astype(dtype) for k in METRICS})
-        h["want"] = _ref(h, size, halo)
-        for a in (*h["want"], *(h[k] for k in SHARED)):
-            a.setflags(write=False)
-        _CASES[case] = h
-    return _CASES[case]
+    return H._case(KERNEL, case)
 
 
 def _device(h, gpu, offset=0):
-    return {k: _dev(h[k], gpu, offset) for k in SHARED}
+    return H._device(KERNEL, h, gpu, offset)
 
 
 def _raw_call(osg, gpu, d, Gu, Gv, size, halo, n_fc=None, n_cf=None, value=0.0, scheme=0):
-    lib = osg._lib.momentum_lib()
-    return lib.tpg_momentum_advection_tendency(
-        d["u"].data_ptr(), d["v"].data_ptr(), d["w"].data_ptr(), Gu.data_ptr(), Gv.data_ptr(), *(d[k].data_ptr() for k in METRICS),
-        d["dz_f"].data_ptr(), None if n_fc is None else n_fc.data_ptr(), None if n_cf is None else n_cf.data_ptr(), value, scheme, *size, *halo,
-        osg._lib.ft_of(d["u"].dtype), osg._lib.current_stream_ptr(gpu))
+    return H._launch(osg, gpu, KERNEL, d, {"Gu": Gu, "Gv": Gv}, size, halo, counts=(n_fc, n_cf), value=value, scheme=scheme)
 
 
 def _call(osg, gpu, d, size, halo, n_fc=None, n_cf=None, value=0.0, offset=0):
     """tpg_momentum_advection_tendency on the device arrays d into fresh sentinel-filled outputs -> the whole parents (Gu, Gv) on the host"""
-    T = {torch.float64: F64, torch.float32: F32}[d["u"].dtype]
-    outs = [_dev(np.full(tuple(d["u"].shape), SENTINEL, T), gpu, offset) for _ in range(2)]
-    osg._lib.check_momentum(_raw_call(osg, gpu, d, *outs, size, halo, n_fc, n_cf, value))
-    return [o.cpu().numpy() for o in outs]
-
-
-def _assert_parent(got, want, what):
-    bad = same_bits(got, want)
-    assert bad == 0, (what, bad, "cells differ of", got.size)
-
-
-def _assert_pair(got, want, what):
-    for name, g, w_ in zip(("Gu", "Gv"), got, want):
-        _assert_parent(g, w_, (what, name))
-
-
-def _assert_inputs_unchanged(d, h, what):
-    for k in SHARED:
-        _assert_parent(d[k].cpu().numpy(), h[k], (what, "input", k))
+    return H._call(osg, gpu, KERNEL, d, size, halo, None, (n_fc, n_cf), value, offset)
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------------------
@@ -181,30 +110,6 @@ def test_no_cell_outside_the_stencil_is_read(osg, gpu, case, offset):
     _assert_pair(got, h["want"], "poisoned")
 
 
-_PLANES = {}
-
-
-def _count_planes(case):
-    """(Face, Center) and (Center, Face) count planes for two drawn bottoms (land columns, open columns, everything between), each with a
-    count above Nz and a negative one planted (planes of a deeper grid; a column the counts call never writes).  Computed once per case."""
-    if case in _PLANES:
-        return _PLANES[case]
-    size, halo, dtype = case
-    Nx, Ny, Nz = size
-    planes = []
-    for q in (0, 1):
-        rng = np.random.default_rng([11 + q, *size, *halo])
-        n = draw_columns(rng, Nx, Ny, Nz).astype(np.int32)
-        n[Ny - 1 - q, Nx - 1] = Nz + 3
-        n[q, 0] = -2
-        assert n.shape == (Ny, Nx) and (n == 0).any() and (n == Nz).any() and (Nz < 2 or ((n > 0) & (n < Nz)).any())
-        n.setflags(write=False)
-        planes.append(n)
-    assert (planes[0] != planes[1]).any()
-    _PLANES[case] = tuple(planes)
-    return _PLANES[case]
-
-
 @pytest.mark.parametrize("case,offset", [(c, 0) for c in SMALL] + [(OFFSET[0], 1)], ids=[_id(c) for c in SMALL] + [_id(OFFSET[0]) + "-offset"])
 def test_fused_mask_equals_the_reference_and_the_mask_pass(osg, gpu, case, offset):
     """with the count planes: (1) the reference with the mask; (2) the unmasked call followed by tpg_mask_immersed_fields on Gu (by n_fc) and
@@ -213,7 +118,7 @@ def test_fused_mask_equals_the_reference_and_the_mask_pass(osg, gpu, case, offse
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     h = _case(case)
     nfc, ncf = _count_planes(case)
-    want = _ref(h, size, halo, nfc, ncf, MASK_VALUE)
+    want = _ref(h, size, halo, nfc, ncf)
     inner = lambda a: a[Hz:Hz + Nz, Hy:Hy + Ny, Hx:Hx + Nx]        # noqa: E731
     assert (inner(want[0])[:, Ny - 1, Nx - 1] == dtype(MASK_VALUE)).all() and (inner(want[1])[:, Ny - 2, Nx - 1] == dtype(MASK_VALUE)).all()
     assert same_bits(inner(want[0])[:, 0, 0], inner(h["want"][0])[:, 0, 0]) == 0         # n < 0: nothing
@@ -305,42 +210,6 @@ def test_error_returns_on_device_pointers(osg, gpu):
 DT, CHI = 0.01, 0.1
 
 
-def _filled(osg, like, interior, base):
-    """the parent fill_halo_regions gives a field at `like`'s location and grid that held `base` (a parent) and got that interior"""
-    f = osg.Field(like.loc, like.grid, boundary_conditions=like.boundary_conditions)
-    f.data.copy_(torch.from_numpy(np.ascontiguousarray(base)).reshape(f.data.shape))
-    f.interior().copy_(torch.from_numpy(np.ascontiguousarray(interior)).reshape(f.interior().shape))
-    osg.fill_halo_regions([f])
-    return f.data.cpu().numpy()
-
-
-def _model(osg, gpu, size, halo, tdt, immersed, seed=3):
-    """(grid, u, v, w, Gu, Gv, Gum, Gvm): filled u, v, w from compute_w_from_continuity (its horizontal halos filled), random tendencies"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    grid = osg.TripolarGrid(osg.GPU(0), tdt, size=size, halo=halo, z=(-1, 0))
-    if immersed:
-        zc = grid.z_centers[Hz:Hz + Nz].cpu().numpy()
-        rng = np.random.default_rng(19)
-        grid = osg.ImmersedBoundaryGrid(grid, osg.GridFittedBottom(heights_of(draw_columns(rng, Nx, Ny, Nz), zc, rng)))
-    gen = torch.Generator(device=gpu).manual_seed(seed)
-    u, Gu, Gum = (osg.XFaceField(grid) for _ in range(3))
-    v, Gv, Gvm = (osg.YFaceField(grid) for _ in range(3))
-    for f in (u, v, Gu, Gv, Gum, Gvm):
-        f.data.uniform_(-1, 1, generator=gen)
-    osg.fill_halo_regions([u, v])
-    w = osg.compute_w_from_continuity(u, v)
-    return grid, u, v, w, Gu, Gv, Gum, Gvm
-
-
-def _host_metrics(osg, grid, dtype):
-    g = getattr(grid, "underlying_grid", grid)
-    m = {k: g.arrays[k].cpu().numpy() for k in METRICS}
-    dz = osg.z_all_face_spacings(grid, dtype).numpy().astype(m["dx_fc"].dtype)
-    counts = getattr(grid, "column_counts", None)
-    n = (None, None) if counts is None else (counts["fc"].cpu().numpy(), counts["cf"].cpu().numpy())
-    return m, dz, n
-
-
 @pytest.mark.parametrize("immersed", [False, True], ids=["tripolar", "immersed"])
 @pytest.mark.parametrize("size,halo,tdt", [((48, 40, 6), (5, 5, 5), torch.float64), ((50, 40, 3), (4, 4, 4), torch.float32)],
                          ids=["48x40x6-h5-f64", "50x40x3-h4-f32"])
@@ -351,7 +220,7 @@ def test_two_steps_eagerly_and_as_a_graph_equal_the_references_composed(osg, gpu
     mask_immersed_field's"""
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     grid, u, v, w, Gu, Gv, Gum, Gvm = _model(osg, gpu, size, halo, tdt, immersed)
-    m, dz, (nfc, ncf) = _host_metrics(osg, grid, tdt)
+    m, dz, (nfc, ncf) = _host_metrics(osg, KERNEL, grid, tdt)
     assert (nfc is not None) == immersed
     hw = w.data.cpu().numpy()
     tend = osg.momentum_advection_plan(u, v, w, Gu, Gv)
@@ -367,7 +236,7 @@ def test_two_steps_eagerly_and_as_a_graph_equal_the_references_composed(osg, gpu
             want_Gu, want_Gv = tendencies(u0, v0, hw, Gu0, Gv0, m, dz, size, halo, nfc, ncf, 0.0)
         new_u, prev_u, _ = ab2_ref.ab2_step(u0, want_Gu, Gum0, DT, CHI, ab2_ref.STORE, size, halo)
         new_v, prev_v, _ = ab2_ref.ab2_step(v0, want_Gv, Gvm0, DT, CHI, ab2_ref.STORE, size, halo)
-        new_u, new_v = _filled(osg, u, cut(new_u), u0), _filled(osg, v, cut(new_v), v0)
+        new_u, new_v = _filled(osg, u, cut(new_u), u0, u.boundary_conditions), _filled(osg, v, cut(new_v), v0, v.boundary_conditions)
         want = [new_u, new_v, want_Gu, want_Gv, prev_u, prev_v]
         for name, f, x in zip(("u", "v", "Gu", "Gv", "Gum", "Gvm"), everything, want):
             _assert_parent(f.data.cpu().numpy(), x, (name, it))
@@ -409,7 +278,7 @@ def test_out_is_allocated_or_given_and_filled(osg, gpu):
     size, halo, tdt = (20, 12, 3), (3, 2, 1), torch.float64
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     grid, u, v, w, Gu, Gv, _, _ = _model(osg, gpu, size, halo, tdt, False)
-    m, dz, _ = _host_metrics(osg, grid, tdt)
+    m, dz, _ = _host_metrics(osg, KERNEL, grid, tdt)
     hu, hv, hw = (f.data.cpu().numpy() for f in (u, v, w))
     zero = np.zeros_like(hu)
     want = tendencies(hu, hv, hw, zero, zero, m, dz, size, halo)

@@ -1,7 +1,8 @@
-"""GPU tests of the six tendency kernels where their addressing can go wrong and no other test looks: element offsets at and past 2^31,
+"""GPU tests of the seven tendency kernels where their addressing can go wrong and no other test looks: element offsets at and past 2^31,
 latitude bands, the smallest shapes check_geom admits.  The kernels: the centred, WENO5 x/y and all-WENO tracer tendencies, the
-vector-invariant momentum tendency and its WENO5-upwinded form, the free-surface sub-step -- all driven through the C ABI from ONE adapter
-table (tests/tendency_windows.py: library, symbol, array list, numpy reference).  Every comparison is bit for bit, on whole arrays, on
+vector-invariant momentum tendency, its form with the WENO5-upwinded vorticity term and the one upwinded in every term, the free-surface
+sub-step -- all driven through the C ABI from ONE adapter table (tests/tendency_windows.py: library, symbol, array list, numpy reference)
+by the one launch of tests/gpu_harness.py.  Every comparison is bit for bit, on whole arrays, on
 integer views; there is no tolerance anywhere in this file.  tests/test_tendency_windows_ref.py holds, on the CPU, every fact these
 comparisons rest on: that a cut-out of rows or of planes is a valid stand-in for the whole, on which levels an all-WENO plane window
 agrees with the column, that the comparators notice one wrong bit, and that every address of the smallest shapes lies inside its parent.
@@ -10,91 +11,28 @@ B1, past 2^31 elements: 8640 x 4320 x 64 at halo (4, 4, 4) in Float32, the geome
 2 694 855 168 elements (w one plane more), offset 2^31 falls in padded plane 57 (interior level 54), byte offsets cross 2^33.  One test per
 3-D tendency.  The free-surface sub-step works on 2-D planes, which cannot reach 2^31 elements (check_geom refuses such a plane): it has
 no such test.
-B2, latitude bands: all six kernels.  The free-surface sub-step CARRIES row 1 of V (the south wall row): row 1 of a band that starts inside
+B2, latitude bands: all seven kernels, at 40 x 24 x 3; the tendency upwinded in every term at 40 x 24 x 7, whose seven levels reach every
+class of its z-faces' order table.  The free-surface sub-step CARRIES row 1 of V (the south wall row): row 1 of a band that starts inside
 the domain holds V's input where the global call computed; every other row and array is the global call's.
-B3, the smallest shapes: all six kernels.  The free surface refuses Ny = 1; its smallest is (2, 2, 1)."""
-import contextlib
-import gc
-import time
-
+B3, the smallest shapes: the six kernels of one launch, those with an entry in tendency_windows.SMALLEST (the two-launch tendency upwinded
+in every term, which tendency_windows.walk does not mirror, has its smallest shapes in tests/test_gpu_weno_vi.py).  The free surface refuses Ny = 1; its smallest is (2, 2, 1)."""
 import numpy as np
 import pytest
 import torch
 
 import tendency_windows as tw
-from momentum_ref import METRICS
-from tendency_windows import DTAU, F32, F64, GRAVITY, KERNELS, MASK_VALUE, SENTINEL, WITH_LEVELS, equal_bits, interior
+from gpu_harness import (BIG, BIG_HALO, COMPARED, TWO30, TWO31, _assert_only_the_interior_is_written, _big_counts, _bits_of, _budget,  # noqa: F401
+                         _cell_at, _check, _dev, _free_hbm, _fresh, _launch, _random, _run)
+from tendency_windows import F32, F64, KERNELS, MASK_VALUE, SENTINEL, WITH_LEVELS, equal_bits, interior
 from vorticity_ref import same_bits
 
 pytestmark = pytest.mark.gpu
 
-TWO31, TWO30 = 1 << 31, 1 << 30
 UNSUPPORTED = -5                                   # TPG_ERR_UNSUPPORTED
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
 
 
 def _ids(v):
     return v.name if isinstance(v, tw.Kernel) else {F32: "f32", F64: "f64"}.get(v)
-
-
-# ---- the one way into the six entry points -----------------------------------------------------------------------------------------------------
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _launch(osg, gpu, kernel, d, outs, size, halo, masked):
-    """the status of kernel's entry point on the device arrays d and the outputs outs (both by the names of the adapter table)"""
-    fn = getattr(getattr(osg._lib, kernel.library + "_lib")(), kernel.symbol)
-    n = [_ptr(d[c]) if masked else None for c in kernel.counts]
-    if kernel.counts == ("n_cc",):                                 # the tracer tendencies: tables of one tracer
-        args = [osg._lib.ptr_table([d["c"]]), osg._lib.ptr_table([outs["G"]]), 1, *(d[k].data_ptr() for k in ("u", "v", "w", *kernel.planes, "dz_c")),
-                *n, MASK_VALUE]
-    elif kernel.has_levels:                                        # the momentum tendencies
-        args = [*(d[k].data_ptr() for k in ("u", "v", "w")), outs["Gu"].data_ptr(), outs["Gv"].data_ptr(), *(d[k].data_ptr() for k in METRICS),
-                d["dz_f"].data_ptr(), *n, MASK_VALUE]
-    else:                                                          # the free-surface sub-step, without averaging
-        args = [*(outs[k].data_ptr() for k in kernel.outputs), *(d[k].data_ptr() for k in kernel.planes[:5]), None, None, None,
-                *(d[k].data_ptr() for k in kernel.planes[5:]), d["depth"].data_ptr(), *n, DTAU, GRAVITY, 0.0]
-    if kernel.scheme_arg:
-        args.append(0)
-    geom = (*size, *halo) if kernel.has_levels else (*size, halo[0], halo[1])
-    return fn(*args, *geom, osg._lib.ft_of(outs[kernel.outputs[0]].dtype), osg._lib.current_stream_ptr(gpu))
-
-
-def _check(osg, kernel, status):
-    getattr(osg._lib, "check_" + kernel.library)(status)
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
-
-
-def _fresh(kernel, size, halo, dtype, gpu, offset=0):
-    return {name: _dev(np.full(tw.shape_of(kernel, name, size, halo), SENTINEL, dtype), gpu, offset) for name in kernel.outputs}
-
-
-def _run(osg, gpu, kernel, h, size, halo, masked, offset=0):
-    """the entry point on device copies of the host problem h into fresh sentinel-filled outputs -> the whole outputs on the host"""
-    dtype = h[kernel.planes[0]].dtype.type
-    d = {k: _dev(a, gpu, offset) for k, a in h.items()}
-    outs = _fresh(kernel, size, halo, dtype, gpu, offset)
-    _check(osg, kernel, _launch(osg, gpu, kernel, d, outs, size, halo, masked))
-    return {k: o.cpu().numpy() for k, o in outs.items()}
 
 
 _DRAWN = {}
@@ -116,67 +54,6 @@ def _assert_whole(got, want, what):
 
 
 # ---- B1: past 2^31 elements -----------------------------------------------------------------------------------------------------------------------
-BIG, BIG_HALO = (8640, 4320, 64), (4, 4, 4)
-# the levels each window is compared on: what tests/test_tendency_windows_ref.py::test_the_all_weno_windows_of_the_gpu_test computed.  An
-# all-WENO window of ten leaves out its bottom three levels (unless they are the column's) and its top three (unless they are the column's):
-# their faces have another order in the window than in the column
-COMPARED = {True: {"bottom": [1, 2, 3, 4], "middle": [53, 54, 55, 56], "top": [61, 62, 63, 64]},
-            False: {"bottom": list(range(1, 8)), "middle": [53, 54, 55, 56], "top": list(range(58, 65))}}
-
-
-@contextlib.contextmanager
-def _budget(gpu, what):
-    """wall time and peak device memory of the block, printed; the peak stays under half the card"""
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats(gpu)
-    t0 = time.perf_counter()
-    yield
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated(gpu)
-    print(f"\n[tendency past 2g] {what}: {time.perf_counter() - t0:.1f} s, peak {peak / 2**30:.1f} GiB")
-    assert peak < torch.cuda.get_device_properties(gpu).total_memory / 2, peak
-
-
-def _cell_at(offset, size, halo):
-    """the interior cell (k, j, i), 0-based, that holds element `offset` of a padded parent (asserted: it is an interior cell)"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    sy, sx = Ny + 2 * Hy, Nx + 2 * Hx
-    pk, rem = divmod(offset, sy * sx)
-    pj, pi = divmod(rem, sx)
-    assert Hz <= pk < Hz + Nz and Hy <= pj < Hy + Ny and Hx <= pi < Hx + Nx
-    return pk - Hz, pj - Hy, pi - Hx
-
-
-def _random(gpu, shape, seed, lo, hi):
-    return torch.empty(shape, dtype=torch.float32, device=gpu).uniform_(lo, hi, generator=torch.Generator(device=gpu).manual_seed(seed))
-
-
-def _big_counts(gpu, size, seed):
-    """0 in most columns, drawn from 0 .. Nz in one column of eight, Nz in columns 0 .. 7 of every row: the mask's stores reach the top level
-    (past 2^31) there, the tendency's everywhere else"""
-    Nx, Ny, Nz = size
-    gen = torch.Generator(device=gpu).manual_seed(seed)
-    n = torch.randint(0, Nz + 1, (Ny, Nx), dtype=torch.int32, device=gpu, generator=gen)
-    keep = torch.randint(0, 8, (Ny, Nx), dtype=torch.int32, device=gpu, generator=gen) == 0
-    n = torch.where(keep, n, torch.zeros_like(n))
-    n[:, :8] = Nz
-    return n
-
-
-def _bits_of(value, like):
-    return tw._ints(torch.full((1,), value, dtype=like.dtype, device=like.device))[0]
-
-
-def _assert_only_the_interior_is_written(out, size, halo):
-    """every halo cell still holds the sentinel, no interior cell does: on the device, by narrow, on integer views"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    I, s = tw._ints(out), _bits_of(SENTINEL, out)
-    for dim, x in enumerate((Hz, Hy, Hx)):
-        assert bool((I.narrow(dim, 0, x) == s).all()) and bool((I.narrow(dim, I.shape[dim] - x, x) == s).all()), dim
-    for k0 in range(0, Nz, 8):
-        assert not bool((I[Hz + k0:Hz + min(k0 + 8, Nz), Hy:Hy + Ny, Hx:Hx + Nx] == s).any()), k0
-
-
 @pytest.mark.parametrize("kernel", WITH_LEVELS, ids=_ids)
 def test_float32_past_2g_elements(osg, gpu, kernel):
     """8640 x 4320 x 64, halo 4, Float32, with the fused mask.  Data drawn on the device: velocities and tracer of both signs, metrics and
@@ -253,7 +130,7 @@ def test_float32_past_2g_elements(osg, gpu, kernel):
 
 
 # ---- B2: latitude bands -----------------------------------------------------------------------------------------------------------------------------
-GLOBAL = (40, 24, 3)
+GLOBAL = {k.name: (40, 24, 7 if k.name == "weno_vi" else 3) for k in KERNELS.values()}       # seven levels: every class of weno_vi's z-face orders
 
 
 def _band_halo(kernel, dtype):
@@ -268,12 +145,12 @@ def _band_halo(kernel, dtype):
 @pytest.mark.parametrize("dtype", [F64, F32], ids=_ids)
 @pytest.mark.parametrize("kernel", KERNELS.values(), ids=_ids)
 def test_latitude_bands_equal_the_global_field(osg, gpu, kernel, dtype, layout, masked):
-    """40 x 24 x 3, global parents random in every cell, cut into bands as rows jstart - Hy .. jend + Hy of every array (the count planes,
+    """40 x 24 x 3 (GLOBAL), global parents random in every cell, cut into bands as rows jstart - Hy .. jend + Hy of every array (the count planes,
     which have no halo, by their rows): three bands of 8 rows, and a chain with a band of exactly Hy rows -- one partial tile whose south
     and north stencil arms both leave the band -- beside one of Hy + 1 rows and the rest.  Each band's output equals the matching rows of
     the global DEVICE result, and, as a whole parent, the reference on the cut: the band's own halo rows still hold the sentinel.  (Row 1
     of V of a free-surface band that starts inside the domain is carried: it holds V's input, as the reference on the cut says.)"""
-    size, halo = GLOBAL, _band_halo(kernel, dtype)
+    size, halo = GLOBAL[kernel.name], _band_halo(kernel, dtype)
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     h, want = _problem(kernel, size, halo, dtype)
     glob = _run(osg, gpu, kernel, h, size, halo, masked)
@@ -293,7 +170,7 @@ def test_latitude_bands_equal_the_global_field(osg, gpu, kernel, dtype, layout, 
 
 
 # ---- B3: the smallest legal shapes ---------------------------------------------------------------------------------------------------------------------
-SMALL = [(k, size, halo, dtype) for k in KERNELS.values() for size, halo in tw.SMALLEST[k.name] for dtype in (F64, F32)]
+SMALL = [(k, size, halo, dtype) for k in KERNELS.values() if k.name in tw.SMALLEST for size, halo in tw.SMALLEST[k.name] for dtype in (F64, F32)]
 
 
 def _small_id(case):

@@ -8,15 +8,15 @@ cell); rows off the 16-B grid with an odd Hx (the element-aligned chunks); the m
 shape with more work items than resident threads and Ny no multiple of the rows an item owns (tile edges, the last partial tile); and one
 case past 2^31 elements."""
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
 import torch
 
+from gpu_harness import _assert_parent, _dev, _free_hbm, _id  # noqa: F401
 from immersed_ref import column_counts, draw_columns, heights_of, inactive_cells, peripheral
 from special_values import pool
-from vorticity_ref import cells_read, interior_vorticity, same_bits, vertical_vorticity
+from vorticity_ref import cells_read, interior_vorticity, vertical_vorticity
 
 pytestmark = pytest.mark.gpu
 
@@ -35,33 +35,8 @@ SENTINEL = 12345.0
 MASK_VALUE = 0.1                                   # not representable: converted once to the field type
 
 
-def _id(case):
-    size, halo, dtype = case
-    return "x".join(map(str, size)) + "-h" + "".join(map(str, halo)) + ("-f64" if dtype == F64 else "-f32")
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
 def _tdt(dtype):
     return torch.float64 if dtype == F64 else torch.float32
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
 
 
 def _shapes(size, halo):
@@ -109,11 +84,6 @@ def _device(h, gpu, offset=0):
     d = {k: _dev(h[k], gpu, offset) for k in ("u", "v", "dx_fc", "dy_cf", "az_ff")}
     d["zeta"] = _dev(np.full(h["u"].shape, SENTINEL, h["u"].dtype), gpu, offset)
     return d
-
-
-def _assert_parent(got, want, what):
-    bad = same_bits(got, want)
-    assert bad == 0, (what, bad, "cells differ of", got.size)
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------------------

@@ -12,26 +12,25 @@ Shapes, the smallest at which each path can go wrong:
   is odd: the first launch takes two rows per item and its last tile is partial.  10 x 5 x 6 in Float32: 8-B chunks (Nx = 2 mod 4).
 - 130 x 4 x 2 in Float64 and 260 x 4 x 2 in Float32: 65 chunks a row, so a wave edge (64 | 65), a row end and the periodic seam fall inside
   the arms of the first launch's shared Z and of the second launch's rows.
-- every case compares the rows Ny, Ny - 1, Ny - 2, whose arms reach the rows Ny + 1 .. Ny + 3, random like every other cell."""
+- every case compares the rows Ny, Ny - 1, Ny - 2, whose arms reach the rows Ny + 1 .. Ny + 3, random like every other cell.
+Its latitude bands (40 x 24 x 7) and its test past 2^31 elements are tests/test_gpu_tendency_edges.py's, from its row of the adapter table."""
 import ctypes as C
-import gc
 
 import numpy as np
 import pytest
 import torch
 
 import ab2_ref
+import gpu_harness as H
 import tendency_windows as tw
-import weno_vi_ref as ref
-from immersed_ref import draw_columns, heights_of
+from gpu_harness import (F32, F64, MASK_VALUE, SENTINEL, _assert_inputs_unchanged, _assert_pair, _assert_parent, _count_planes, _dev,  # noqa: F401
+                         _filled, _free_hbm, _host_metrics, _velocity_model as _model)
 from special_values import pool
-from test_gpu_tendency_edges import (BIG, BIG_HALO, COMPARED, TWO30, TWO31, _assert_only_the_interior_is_written, _big_counts, _bits_of,
-                                     _budget, _cell_at, _random)
 from weno_vi_ref import METRICS, cells_read, dependence_window, same_bits, tendencies, terms
 
 pytestmark = pytest.mark.gpu
 
-F32, F64 = np.float32, np.float64
+KERNEL = tw.KERNELS["weno_vi"]
 NZS = (1, 2, 3, 4, 5, 6, 7, 9)
 FORMS = {"aligned": ((4, 4, 4), 0), "offset": ((4, 4, 4), 1), "oddHx": ((3, 3, 1), 0)}
 LEVELS = [(((12, 5, nz), halo, dtype), off, f"12x5x{nz}-{form}-{'f64' if dtype == F64 else 'f32'}")
@@ -44,97 +43,30 @@ EDGES = [(((4, 3, 1), (3, 3, 1), F64), 0, "4x3x1-h331-f64"), (((4, 3, 1), (3, 3,
 ALL = LEVELS + EDGES
 SOME = [c for c in ALL if c[2] in ("12x5x9-aligned-f64", "12x5x9-oddHx-f32", "12x5x7-offset-f64", "12x5x4-aligned-f32", "12x5x1-oddHx-f64",
                                    "130x4x2-h444-f64", "260x4x2-h444-f32", "10x5x6-h444-f32-8B")]
-SENTINEL = 12345.0
-MASK_VALUE = 0.1                                   # not representable: converted once to the field type
 FIELDS = ("u", "v", "w")
 SHARED = (*FIELDS, *METRICS, "dz_c")
 
 
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
-
-
-def _shapes(size, halo):
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    return (Nz + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Nz + 1 + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Ny + 2 * Hy, Nx + 2 * Hx)
-
-
-def _ref(h, size, halo, n_fc=None, n_cf=None, value=0.0):
-    """the reference parents (Gu, Gv) from sentinel-filled ones"""
-    G0 = np.full(h["u"].shape, SENTINEL, h["u"].dtype)
-    with np.errstate(all="ignore"):
-        return tendencies(h["u"], h["v"], h["w"], G0, G0, {k: h[k] for k in METRICS}, h["dz_c"], size, halo, n_fc, n_cf, value)
-
-
-_CASES = {}
+def _ref(h, size, halo, n_fc=None, n_cf=None):
+    """the reference parents (Gu, Gv) from sentinel-filled ones; with the count planes: masked to MASK_VALUE"""
+    return H._ref(KERNEL, h, size, halo, () if n_fc is None else (n_fc, n_cf))
 
 
 def _case(case):
-    """host arrays of a case, random in EVERY cell (halos included), and the reference parents of Gu, Gv from sentinel-filled ones: computed
-    once per case, shared by the tests, never modified (tests copy what they change)"""
-    if case not in _CASES:
-        size, halo, dtype = case
-        parent, wparent, plane = _shapes(size, halo)
-        rng = np.random.default_rng([*size, *halo, np.dtype(dtype).itemsize])
-        h = {"u": rng.uniform(-1, 1, parent).astype(dtype), "v": rng.uniform(-1, 1, parent).astype(dtype),
-             "w": rng.uniform(-1, 1, wparent).astype(dtype), "dz_c": rng.uniform(0.5, 2, size[2]).astype(dtype)}
-        h.update({k: rng.uniform(0.5, 2, plane).astype(dtype) for k in METRICS})
-        h["want"] = _ref(h, size, halo)
-        for a in (*h["want"], *(h[k] for k in SHARED)):
-            a.setflags(write=False)
-        _CASES[case] = h
-    return _CASES[case]
+    return H._case(KERNEL, case)
 
 
 def _device(h, gpu, offset=0):
-    return {k: _dev(h[k], gpu, offset) for k in SHARED}
+    return H._device(KERNEL, h, gpu, offset)
 
 
 def _raw_call(osg, gpu, d, Gu, Gv, size, halo, n_fc=None, n_cf=None, value=0.0, shift_u=0):
-    lib = osg._lib.weno_vi_lib()
-    return lib.tpg_weno_vi_momentum_advection_tendency(
-        d["u"].data_ptr() + shift_u, d["v"].data_ptr(), d["w"].data_ptr(), Gu.data_ptr(), Gv.data_ptr(), *(d[k].data_ptr() for k in METRICS),
-        d["dz_c"].data_ptr(), None if n_fc is None else n_fc.data_ptr(), None if n_cf is None else n_cf.data_ptr(), value, *size, *halo,
-        osg._lib.ft_of(d["u"].dtype), osg._lib.current_stream_ptr(gpu))
+    return H._launch(osg, gpu, KERNEL, d, {"Gu": Gu, "Gv": Gv}, size, halo, counts=(n_fc, n_cf), value=value, shift=("u", shift_u))
 
 
 def _call(osg, gpu, d, size, halo, n_fc=None, n_cf=None, value=0.0, offset=0):
     """tpg_weno_vi_momentum_advection_tendency on the device arrays d into fresh sentinel-filled outputs -> the whole parents (Gu, Gv) on the host"""
-    T = {torch.float64: F64, torch.float32: F32}[d["u"].dtype]
-    outs = [_dev(np.full(tuple(d["u"].shape), SENTINEL, T), gpu, offset) for _ in range(2)]
-    osg._lib.check_weno_vi(_raw_call(osg, gpu, d, *outs, size, halo, n_fc, n_cf, value))
-    return [o.cpu().numpy() for o in outs]
-
-
-def _assert_parent(got, want, what):
-    bad = same_bits(got, want)
-    assert bad == 0, (what, bad, "cells differ of", got.size)
-
-
-def _assert_pair(got, want, what):
-    for name, g, w_ in zip(("Gu", "Gv"), got, want):
-        _assert_parent(g, w_, (what, name))
-
-
-def _assert_inputs_unchanged(d, h, what):
-    for k in SHARED:
-        _assert_parent(d[k].cpu().numpy(), h[k], (what, "input", k))
+    return H._call(osg, gpu, KERNEL, d, size, halo, None, (n_fc, n_cf), value, offset)
 
 
 def _params(cases):
@@ -206,28 +138,6 @@ def test_domain_of_dependence_without_an_oracle(osg, gpu, positive):
     assert len(sizes) == 16 and sum(n > 0 for n in sizes) >= 10 and max(sizes) >= 15, sizes
 
 
-_PLANES = {}
-
-
-def _count_planes(case):
-    """(Face, Center) and (Center, Face) count planes for two drawn bottoms, each with a count above Nz and a negative one planted"""
-    if case in _PLANES:
-        return _PLANES[case]
-    size, halo, dtype = case
-    Nx, Ny, Nz = size
-    planes = []
-    for q in (0, 1):
-        rng = np.random.default_rng([11 + q, *size, *halo])
-        n = draw_columns(rng, Nx, Ny, Nz).astype(np.int32)
-        n[Ny - 1 - q, Nx - 1] = Nz + 3
-        n[q, 0] = -2
-        n.setflags(write=False)
-        planes.append(n)
-    assert (planes[0] != planes[1]).any()
-    _PLANES[case] = tuple(planes)
-    return _PLANES[case]
-
-
 @_params(SOME)
 def test_fused_mask_equals_the_reference_and_the_mask_pass(osg, gpu, case, offset):
     """with the count planes: (1) the reference with the mask; (2) the unmasked result followed by tpg_mask_immersed_fields on Gu (by n_fc)
@@ -235,8 +145,8 @@ def test_fused_mask_equals_the_reference_and_the_mask_pass(osg, gpu, case, offse
     size, halo, dtype = case
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     h = _case(case)
-    nfc, ncf = _count_planes(case)
-    want = _ref(h, size, halo, nfc, ncf, MASK_VALUE)
+    nfc, ncf = _count_planes(case, varied=False)
+    want = _ref(h, size, halo, nfc, ncf)
     inner = lambda a: a[Hz:Hz + Nz, Hy:Hy + Ny, Hx:Hx + Nx]        # noqa: E731
     assert (inner(want[0])[:, Ny - 1, Nx - 1] == dtype(MASK_VALUE)).all() and (inner(want[1])[:, Ny - 2, Nx - 1] == dtype(MASK_VALUE)).all()
     assert same_bits(inner(want[0])[:, 0, 0], inner(h["want"][0])[:, 0, 0]) == 0         # n < 0: nothing
@@ -361,7 +271,7 @@ def test_error_returns_on_device_pointers(osg, gpu):
     lib = osg._lib.weno_vi_lib()
     err = lambda: lib.tpg_weno_vi_last_error().decode()           # noqa: E731
     out = [_dev(np.full(h["u"].shape, SENTINEL, dtype), gpu) for _ in range(2)]
-    n = _dev(_count_planes(case)[0], gpu)
+    n = _dev(_count_planes(case, varied=False)[0], gpu)
     assert _raw_call(osg, gpu, d, out[0], d["u"], size, halo) == -1 and err().startswith("Gv overlaps u")
     assert _raw_call(osg, gpu, d, d["w"], out[1], size, halo) == -1 and err().startswith("Gu overlaps w")
     assert _raw_call(osg, gpu, d, out[0], out[0], size, halo) == -1 and err() == "Gv overlaps Gu"
@@ -377,157 +287,8 @@ def test_error_returns_on_device_pointers(osg, gpu):
     _assert_inputs_unchanged(d, h, "refusals")
 
 
-# ---- addressing edges: latitude bands, past 2^31 elements ----------------------------------------------------------------------------------------
-def _vi_ref(h, size, halo, masked):
-    n = (h["n_fc"], h["n_cf"]) if masked else (None, None)
-    G0 = np.full(h["u"].shape, SENTINEL, h["u"].dtype)
-    with np.errstate(all="ignore"):
-        Gu, Gv = tendencies(h["u"], h["v"], h["w"], G0, G0, {k: h[k] for k in METRICS}, h["dz_c"], size, halo, *n, MASK_VALUE)
-    return {"Gu": Gu, "Gv": Gv}
-
-
-# a row of tests/tendency_windows.py's adapter table for this call: its cut-outs, shapes and window levels are that module's
-KERNEL = tw.Kernel("weno_vi", "weno_vi", "tpg_weno_vi_momentum_advection_tendency", fields=("u", "v"), tall=("w",), planes=METRICS,
-                   signed=("u", "v", "w"), column=("dz_c", 0), counts=("n_fc", "n_cf"), outputs=("Gu", "Gv"), out_rank=3, arm=(3, 3, 1),
-                   centred_in_z=False, scheme_arg=False, jt={8: 1, 4: 1}, share=False, ref=_vi_ref)
-
-
-def _launch(osg, gpu, d, outs, size, halo, masked):
-    fn = osg._lib.weno_vi_lib().tpg_weno_vi_momentum_advection_tendency
-    n = [d[c].data_ptr() if masked else None for c in KERNEL.counts]
-    return fn(*(d[k].data_ptr() for k in FIELDS), outs["Gu"].data_ptr(), outs["Gv"].data_ptr(), *(d[k].data_ptr() for k in METRICS),
-              d["dz_c"].data_ptr(), *n, MASK_VALUE, *size, *halo, osg._lib.ft_of(outs["Gu"].dtype), osg._lib.current_stream_ptr(gpu))
-
-
-def _run(osg, gpu, h, size, halo, masked):
-    dtype = h["u"].dtype.type
-    d = {k: _dev(a, gpu) for k, a in h.items()}
-    outs = {name: _dev(np.full(tw.shape_of(KERNEL, name, size, halo), SENTINEL, dtype), gpu) for name in KERNEL.outputs}
-    osg._lib.check_weno_vi(_launch(osg, gpu, d, outs, size, halo, masked))
-    return {k: o.cpu().numpy() for k, o in outs.items()}
-
-
-@pytest.mark.parametrize("masked", [False, True], ids=["plain", "masked"])
-@pytest.mark.parametrize("layout", ["three", "thin"])
-@pytest.mark.parametrize("dtype", [F64, F32], ids=["f64", "f32"])
-def test_latitude_bands_equal_the_global_field(osg, gpu, dtype, layout, masked):
-    """40 x 24 x 7, global parents random in every cell, cut into bands as rows jstart - Hy .. jend + Hy of every array: three bands of 8
-    rows, and a chain with a band of exactly Hy rows beside one of Hy + 1 rows and the rest.  Each band's output equals the matching rows
-    of the global DEVICE result and, as a whole parent, the reference on the cut"""
-    size, halo = (40, 24, 7), ((4, 4, 4) if dtype == F64 else (3, 3, 1))
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    h = tw.draw(KERNEL, size, halo, dtype)
-    glob = _run(osg, gpu, h, size, halo, masked)
-    want = _vi_ref(h, size, halo, masked)
-    for name in want:
-        _assert_parent(glob[name], want[name], ("global", name))
-    bands = tw.band_layouts(Ny, Hy)[layout]
-    assert sum(rows for _, rows in bands) == Ny and (layout != "thin" or (bands[0][1], bands[1][1]) == (Hy, Hy + 1))
-    for lo, rows in bands:
-        cut, bsize = tw.row_cut(KERNEL, h, size, halo, lo, rows)
-        got = _run(osg, gpu, cut, bsize, halo, masked)
-        wantb = _vi_ref(cut, bsize, halo, masked)
-        for name in KERNEL.outputs:
-            _assert_parent(got[name], wantb[name], ("band parent", name, lo, rows))
-            g, w = tw.interior(KERNEL, got[name], bsize, halo), tw.interior(KERNEL, glob[name], size, halo)[..., lo:lo + rows, :]
-            assert same_bits(g, w) == 0, ("band against global", name, lo, rows)
-
-
-def test_float32_past_2g_elements(osg, gpu):
-    """8640 x 4320 x 64, halo 4, Float32, with the fused mask, in the manner of tests/test_gpu_tendency_edges.py (its helpers, its
-    geometry): a. every halo cell of Gu, Gv still holds the sentinel, no interior cell does; b. the same entry point on three plane windows
-    of ten levels -- contiguous plane slices of the SAME tensors -- equals the big output on the levels whose faces keep their order
-    (bottom below 2^30, middle around offset 2^31, top at the wall); c. numpy strips of 16 rows around the row that holds offset 2^31 and
-    at the last rows of the top window equal the big output there."""
-    kernel, size, halo = KERNEL, BIG, BIG_HALO
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    plane = (Ny + 2 * Hy) * (Nx + 2 * Hx)
-    k31, j31, i31 = _cell_at(TWO31, size, halo)
-    windows = tw.b1_windows(kernel, Nz, k31 + 1)
-    with _budget(gpu, kernel.name):
-        d = {}
-        for seed, name in enumerate(kernel.inputs()):
-            lo, hi = (-1.0, 1.0) if name in kernel.signed else (0.5, 2.0)
-            d[name] = _random(gpu, tw.shape_of(kernel, name, size, halo), 100 + seed, lo, hi)
-        for seed, name in enumerate(kernel.counts):
-            d[name] = _big_counts(gpu, size, 200 + seed)
-        outs = {name: torch.full(tw.shape_of(kernel, name, size, halo), SENTINEL, dtype=torch.float32, device=gpu) for name in kernel.outputs}
-        osg._lib.check_weno_vi(_launch(osg, gpu, d, outs, size, halo, True))
-        torch.cuda.synchronize()
-        mv = _bits_of(MASK_VALUE, outs["Gu"])
-        for name, out in outs.items():
-            _assert_only_the_interior_is_written(out, size, halo)
-            top = tw._ints(out)[Hz + Nz - 1, Hy:Hy + Ny, Hx:Hx + Nx]
-            assert bool((top[:, :8] == mv).all()) and not bool((top[:, 8:] == mv).all()), name
-        compared = COMPARED[False]
-        for which, (a, b) in windows.items():
-            levels = tw.levels_that_agree(kernel, a, b, Nz)
-            assert levels and levels == compared[which], (which, levels)
-            cut, csize = tw.plane_cut(kernel, d, size, halo, a, b)
-            wouts = {name: torch.full(tw.shape_of(kernel, name, csize, halo), SENTINEL, dtype=torch.float32, device=gpu) for name in kernel.outputs}
-            if which == "bottom":
-                assert (b + 1 + 2 * Hz) * plane < TWO30
-            if which == "top":
-                assert (a - 1 + Hz) * plane > TWO31 and b == Nz
-            osg._lib.check_weno_vi(_launch(osg, gpu, cut, wouts, csize, halo, True))
-            torch.cuda.synchronize()
-            for name in kernel.outputs:
-                for k in levels:
-                    assert tw.equal_bits(wouts[name][Hz + k - a], outs[name][Hz + k - 1]), (which, name, k)
-            del cut, wouts
-        assert k31 + 1 in compared["middle"] and Nz in compared["top"]
-        for which, lo in (("middle", min(max(j31 - 8, 0), Ny - 16)), ("top", Ny - 16)):
-            a, b = windows[which]
-            window, wsize = tw.plane_cut(kernel, d, size, halo, a, b)
-            strip, ssize = tw.row_cut(kernel, window, wsize, halo, lo, 16)
-            host = {name: t.contiguous().cpu().numpy() for name, t in strip.items()}
-            want = _vi_ref(host, ssize, halo, True)
-            for name in kernel.outputs:
-                for k in compared[which]:
-                    got = outs[name][Hz + k - 1, Hy + lo:Hy + lo + 16, Hx:Hx + Nx].contiguous().cpu().numpy()
-                    bad = same_bits(got, want[name][Hz + k - a, Hy:Hy + 16, Hx:Hx + Nx])
-                    assert bad == 0, (which, name, k, bad, "cells differ of", got.size)
-            del window, strip, host, want
-        del d, outs
-
-
 # ---- the package ---------------------------------------------------------------------------------------------------------------------------
 DT, CHI = 0.01, 0.1
-
-
-def _filled(osg, like, interior, base):
-    f = osg.Field(like.loc, like.grid, boundary_conditions=like.boundary_conditions)
-    f.data.copy_(torch.from_numpy(np.ascontiguousarray(base)).reshape(f.data.shape))
-    f.interior().copy_(torch.from_numpy(np.ascontiguousarray(interior)).reshape(f.interior().shape))
-    osg.fill_halo_regions([f])
-    return f.data.cpu().numpy()
-
-
-def _model(osg, gpu, size, halo, tdt, immersed, seed=3):
-    """(grid, u, v, w, Gu, Gv, Gum, Gvm): filled u, v, w from compute_w_from_continuity (its horizontal halos filled), random tendencies"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    grid = osg.TripolarGrid(osg.GPU(0), tdt, size=size, halo=halo, z=(-1, 0))
-    if immersed:
-        zc = grid.z_centers[Hz:Hz + Nz].cpu().numpy()
-        rng = np.random.default_rng(19)
-        grid = osg.ImmersedBoundaryGrid(grid, osg.GridFittedBottom(heights_of(draw_columns(rng, Nx, Ny, Nz), zc, rng)))
-    gen = torch.Generator(device=gpu).manual_seed(seed)
-    u, Gu, Gum = (osg.XFaceField(grid) for _ in range(3))
-    v, Gv, Gvm = (osg.YFaceField(grid) for _ in range(3))
-    for f in (u, v, Gu, Gv, Gum, Gvm):
-        f.data.uniform_(-1, 1, generator=gen)
-    osg.fill_halo_regions([u, v])
-    w = osg.compute_w_from_continuity(u, v)
-    return grid, u, v, w, Gu, Gv, Gum, Gvm
-
-
-def _host_metrics(osg, grid, dtype):
-    g = getattr(grid, "underlying_grid", grid)
-    m = {k: g.arrays[k].cpu().numpy() for k in METRICS}
-    dz = osg.z_center_spacings(grid, dtype).numpy().astype(m["dx_fc"].dtype)
-    counts = getattr(grid, "column_counts", None)
-    n = (None, None) if counts is None else (counts["fc"].cpu().numpy(), counts["cf"].cpu().numpy())
-    return m, dz, n
 
 
 @pytest.mark.parametrize("immersed", [False, True], ids=["tripolar", "immersed"])
@@ -540,7 +301,7 @@ def test_two_steps_eagerly_and_as_a_graph_equal_the_references_composed(osg, gpu
     call is mask_immersed_field's"""
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     grid, u, v, w, Gu, Gv, Gum, Gvm = _model(osg, gpu, size, halo, tdt, immersed)
-    m, dz, (nfc, ncf) = _host_metrics(osg, grid, tdt)
+    m, dz, (nfc, ncf) = _host_metrics(osg, KERNEL, grid, tdt)
     assert (nfc is not None) == immersed and dz.shape == (Nz,)
     hw = w.data.cpu().numpy()
     tend = osg.weno_vi_momentum_advection_plan(u, v, w, Gu, Gv)
@@ -556,7 +317,7 @@ def test_two_steps_eagerly_and_as_a_graph_equal_the_references_composed(osg, gpu
             want_Gu, want_Gv = tendencies(u0, v0, hw, Gu0, Gv0, m, dz, size, halo, nfc, ncf, 0.0)
         new_u, prev_u, _ = ab2_ref.ab2_step(u0, want_Gu, Gum0, DT, CHI, ab2_ref.STORE, size, halo)
         new_v, prev_v, _ = ab2_ref.ab2_step(v0, want_Gv, Gvm0, DT, CHI, ab2_ref.STORE, size, halo)
-        new_u, new_v = _filled(osg, u, cut(new_u), u0), _filled(osg, v, cut(new_v), v0)
+        new_u, new_v = _filled(osg, u, cut(new_u), u0, u.boundary_conditions), _filled(osg, v, cut(new_v), v0, v.boundary_conditions)
         want = [new_u, new_v, want_Gu, want_Gv, prev_u, prev_v]
         for name, f, x in zip(("u", "v", "Gu", "Gv", "Gum", "Gvm"), everything, want):
             _assert_parent(f.data.cpu().numpy(), x, (name, it))
@@ -599,7 +360,7 @@ def test_out_is_allocated_or_given_and_filled(osg, gpu):
     size, halo, tdt = (20, 12, 5), (3, 3, 1), torch.float64
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     grid, u, v, w, Gu, Gv, _, _ = _model(osg, gpu, size, halo, tdt, False)
-    m, dz, _ = _host_metrics(osg, grid, tdt)
+    m, dz, _ = _host_metrics(osg, KERNEL, grid, tdt)
     hu, hv, hw = (f.data.cpu().numpy() for f in (u, v, w))
     zero = np.zeros_like(hu)
     with np.errstate(all="ignore"):

@@ -8,7 +8,6 @@ Shapes: the horizontal sizes, halos and types of tests/test_gpu_weno.py's SMALL 
 than Hx, 8-B chunks, Ny odd, the model halo, 63 and 64 chunks a row) crossed with Nz in {1, 2, 3, 4, 5, 6, 7, 9}: one level (two centred
 faces), the levels at which the orders 1, 3 and 5 first appear, one more of each, and nine (three faces of order 5 in a row: the window has
 moved through all its slots).  dz_c and the metrics are random in [0.5, 2], u, v, w of both signs -- w in every column and chunk."""
-import gc
 import importlib.util
 import os
 
@@ -16,13 +15,16 @@ import numpy as np
 import pytest
 import torch
 
-from immersed_ref import draw_columns, heights_of
+import gpu_harness as H
+import tendency_windows as tw
+from gpu_harness import (F32, F64, MASK_VALUE, SENTINEL, _assert_parent, _count_plane, _dev, _free_hbm, _host_model, _id,  # noqa: F401
+                         _tracer_model as _model)
 from special_values import pool
 from weno_xyz_ref import cells_read, dependence_window, face_order, same_bits, tendency
 
 pytestmark = pytest.mark.gpu
 
-F32, F64 = np.float32, np.float64
+KERNEL = tw.KERNELS["weno_xyz"]
 LEVELS = (1, 2, 3, 4, 5, 6, 7, 9)
 #          (Nx, Ny)   halo       element type
 FORMS = [((10, 10), (4, 4, 4), F64),               # two chunk rows of five
@@ -39,102 +41,31 @@ FORMS = [((10, 10), (4, 4, 4), F64),               # two chunk rows of five
          ((252, 5), (4, 4, 4), F32)]               # 63 chunks of 16 B
 CASES = [((nx, ny, nz), halo, dtype) for (nx, ny), halo, dtype in FORMS for nz in LEVELS]
 OFFSET = [((20, 11, 9), (4, 4, 4), F64), ((48, 40, 6), (5, 5, 5), F64), ((50, 40, 7), (4, 4, 4), F32)]   # every pointer one element off the 16-B grid
-SENTINEL = 12345.0
-MASK_VALUE = 0.1                                   # not representable: converted once to the field type
 NTRACERS = 3
 SHARED = ("u", "v", "w", "dy_fc", "dx_cf", "az_cc", "dz_c")
 
 
-def _id(case):
-    size, halo, dtype = case
-    return "x".join(map(str, size)) + "-h" + "".join(map(str, halo)) + ("-f64" if dtype == F64 else "-f32")
-
-
-@pytest.fixture(autouse=True)
-def _free_hbm():
-    gc.collect()
-    torch.cuda.empty_cache()
-    yield
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
-def _dev(host, gpu, offset=0):
-    """device copy of `host`, `offset` elements past an allocation (element-aligned, off the 16-B grid for offset 1)"""
-    host = np.ascontiguousarray(host)
-    if not host.flags.writeable:
-        host = host.copy()                                         # torch.from_numpy wants a writable array
-    t = torch.empty(host.size + offset, dtype=torch.from_numpy(host.reshape(-1)[:1]).dtype, device=gpu)[offset:].view(host.shape)
-    t.copy_(torch.from_numpy(host))
-    assert offset == 0 or t.data_ptr() % 16 != 0
-    return t
-
-
-def _shapes(size, halo):
-    """(parent of c, G, u, v; parent of w; plane)"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    return (Nz + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Nz + 1 + 2 * Hz, Ny + 2 * Hy, Nx + 2 * Hx), (Ny + 2 * Hy, Nx + 2 * Hx)
-
-
-def _ref(h, c, size, halo, n_cc=None, value=0.0, module_tendency=tendency):
-    """the reference parent of G of the tracer `c` from a sentinel-filled one"""
-    with np.errstate(all="ignore"):
-        return module_tendency(c, h["u"], h["v"], h["w"], np.full(c.shape, SENTINEL, c.dtype), h["dy_fc"], h["dx_cf"], h["az_cc"], h["dz_c"], size,
-                               halo, n_cc, value)
-
-
-_CASES = {}
+def _ref(h, c, size, halo, n_cc=None):
+    """the reference parent of G of the tracer `c` from a sentinel-filled one; with a count plane: masked to MASK_VALUE"""
+    return H._ref(KERNEL, h, size, halo, () if n_cc is None else (n_cc,), c)
 
 
 def _case(case, ntracers=NTRACERS):
-    """host arrays of a case, random in EVERY cell (halos included), and the reference parents of G from sentinel-filled ones: computed once
-    per case, shared by the tests, never modified (tests copy what they change)"""
-    key = (case, ntracers)
-    if key not in _CASES:
-        size, halo, dtype = case
-        parent, wparent, plane = _shapes(size, halo)
-        rng = np.random.default_rng([*size, *halo, np.dtype(dtype).itemsize])
-        h = {"u": rng.uniform(-1, 1, parent).astype(dtype), "v": rng.uniform(-1, 1, parent).astype(dtype),
-             "w": rng.uniform(-1, 1, wparent).astype(dtype),
-             "dy_fc": rng.uniform(0.5, 2, plane).astype(dtype), "dx_cf": rng.uniform(0.5, 2, plane).astype(dtype),
-             "az_cc": rng.uniform(0.5, 2, plane).astype(dtype), "dz_c": rng.uniform(0.5, 2, size[2]).astype(dtype)}
-        h["c"] = [rng.uniform(-1, 1, parent).astype(dtype) for _ in range(ntracers)]
-        h["want"] = [_ref(h, c, size, halo) for c in h["c"]]
-        for a in (*h["c"], *h["want"], *(h[k] for k in SHARED)):
-            a.setflags(write=False)
-        _CASES[key] = h
-    return _CASES[key]
+    return H._case(KERNEL, case, ntracers)
 
 
 def _device(h, gpu, offset=0):
-    d = {k: _dev(h[k], gpu, offset) for k in SHARED}
-    d["c"] = [_dev(c, gpu, offset) for c in h["c"]]
-    return d
+    return H._device(KERNEL, h, gpu, offset)
 
 
-def _raw_call(osg, gpu, d, tracers, outs, size, halo, n_cc=None, value=0.0, which="weno_xyz"):
-    lib, name = ((osg._lib.weno_xyz_lib(), "tpg_weno_xyz_tracer_advection_tendency") if which == "weno_xyz"
-                 else (osg._lib.weno_lib(), "tpg_weno_tracer_advection_tendency"))
-    return getattr(lib, name)(
-        osg._lib.ptr_table(tracers), osg._lib.ptr_table(outs), len(tracers), d["u"].data_ptr(), d["v"].data_ptr(), d["w"].data_ptr(),
-        d["dy_fc"].data_ptr(), d["dx_cf"].data_ptr(), d["az_cc"].data_ptr(), d["dz_c"].data_ptr(), None if n_cc is None else n_cc.data_ptr(),
-        value, *size, *halo, osg._lib.ft_of(d["u"].dtype), osg._lib.current_stream_ptr(gpu))
+def _raw_call(osg, gpu, d, tracers, outs, size, halo, n_cc=None, value=0.0):
+    return H._launch(osg, gpu, KERNEL, dict(d, c=tracers), {"G": outs}, size, halo, counts=(n_cc,), value=value)
 
 
 def _call(osg, gpu, d, size, halo, which=None, n_cc=None, value=0.0, offset=0, library="weno_xyz"):
-    """the call on the tracers `which` (indices; None: all) of the device arrays d into fresh sentinel-filled outputs -> the whole parents
-    of G on the host"""
-    tracers = d["c"] if which is None else [d["c"][q] for q in which]
-    T = {torch.float64: F64, torch.float32: F32}[d["u"].dtype]
-    outs = [_dev(np.full(tuple(t.shape), SENTINEL, T), gpu, offset) for t in tracers]
-    check = osg._lib.check_weno_xyz if library == "weno_xyz" else osg._lib.check_weno
-    check(_raw_call(osg, gpu, d, tracers, outs, size, halo, n_cc, value, library))
-    return [o.cpu().numpy() for o in outs]
-
-
-def _assert_parent(got, want, what):
-    bad = same_bits(got, want)
-    assert bad == 0, (what, bad, "cells differ of", got.size)
+    """the call (of `library`: this tendency's, or the x-y one's) on the tracers `which` (indices; None: all) of the device arrays d into
+    fresh sentinel-filled outputs -> the whole parents of G on the host"""
+    return H._call(osg, gpu, tw.KERNELS[library], d, size, halo, which, (n_cc,), value, offset)
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------------------
@@ -287,26 +218,6 @@ def test_special_values_in_read_cells(osg, gpu, case):
     _assert_parent(_call(osg, gpu, _device(sub, gpu), size, halo)[0], _ref(sub, sub["c"][0], size, halo), "subnormal tracer")
 
 
-_PLANES = {}
-
-
-def _count_plane(case):
-    """a (Center, Center) count plane for a drawn bottom (land columns, open columns, everything between) with a count above Nz and a
-    negative one planted.  Computed once per case."""
-    if case in _PLANES:
-        return _PLANES[case]
-    size, halo, dtype = case
-    Nx, Ny, Nz = size
-    rng = np.random.default_rng([11, *size, *halo])
-    n = draw_columns(rng, Nx, Ny, Nz).astype(np.int32)
-    n[Ny - 1, Nx - 1] = Nz + 3
-    n[0, 0] = -2
-    assert n.shape == (Ny, Nx) and (n == 0).any() and (n == Nz).any() and (Nz < 2 or ((n > 0) & (n < Nz)).any())
-    n.setflags(write=False)
-    _PLANES[case] = n
-    return n
-
-
 MASKED = [((20, 12, 7), (3, 3, 1), F64), ((20, 12, 4), (3, 3, 1), F32), ((22, 6, 2), (3, 3, 1), F32), ((20, 11, 9), (4, 4, 4), F64),
           ((48, 40, 6), (5, 5, 5), F32), ((126, 5, 3), (4, 4, 4), F64), ((10, 10, 1), (4, 4, 4), F64)]
 
@@ -319,7 +230,7 @@ def test_fused_mask_equals_the_reference(osg, gpu, case, offset):
     (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
     h = _case(case)
     n = _count_plane(case)
-    want = [_ref(h, c, size, halo, n, MASK_VALUE) for c in h["c"]]
+    want = [_ref(h, c, size, halo, n) for c in h["c"]]
     inner = lambda a: a[Hz:Hz + Nz, Hy:Hy + Ny, Hx:Hx + Nx]
     assert (inner(want[0])[:, Ny - 1, Nx - 1] == dtype(MASK_VALUE)).all()                # n > Nz: the whole column
     assert same_bits(inner(want[0])[:, 0, 0], inner(h["want"][0])[:, 0, 0]) == 0         # n < 0: nothing
@@ -367,36 +278,6 @@ def test_domain_of_dependence_in_z(osg, gpu, dtype, positive):
 
 # ---- the package ---------------------------------------------------------------------------------------------------------------------------
 DT, CHI = 0.01, 0.1
-
-
-def _model(osg, gpu, size, halo, tdt, immersed, ntracers=2, seed=3):
-    """(grid, tracers, u, v, w, G, Gm): filled c, u, v, w from compute_w_from_continuity, random tendencies"""
-    (Nx, Ny, Nz), (Hx, Hy, Hz) = size, halo
-    grid = osg.TripolarGrid(osg.GPU(0), tdt, size=size, halo=halo, z=(-1, 0))
-    if immersed:
-        zc = grid.z_centers[Hz:Hz + Nz].cpu().numpy()
-        rng = np.random.default_rng(19)
-        grid = osg.ImmersedBoundaryGrid(grid, osg.GridFittedBottom(heights_of(draw_columns(rng, Nx, Ny, Nz), zc, rng)))
-    gen = torch.Generator(device=gpu).manual_seed(seed)
-    u, v = osg.XFaceField(grid), osg.YFaceField(grid)
-    tracers, G, Gm = ([osg.CenterField(grid) for _ in range(ntracers)] for _ in range(3))
-    for f in (u, v, *tracers, *G, *Gm):
-        f.data.uniform_(-1, 1, generator=gen)
-    osg.fill_halo_regions([u, v, *tracers])
-    w = osg.compute_w_from_continuity(u, v)
-    return grid, tracers, u, v, w, G, Gm
-
-
-def _host_model(osg, grid, u, v, w):
-    """host copies of u, v, w, the grid's own metric arrays and spacings and the count plane"""
-    g = getattr(grid, "underlying_grid", grid)
-    h = {"u": u.data.cpu().numpy(), "v": v.data.cpu().numpy(), "w": w.data.cpu().numpy()}
-    for k in ("dy_fc", "dx_cf", "az_cc"):
-        h[k] = g.arrays[k].cpu().numpy()
-    h["dz_c"] = osg.z_center_spacings(grid, u.data.dtype).numpy().astype(h["u"].dtype)
-    counts = getattr(grid, "column_counts", None)
-    h["n_cc"] = None if counts is None else counts["cc"].cpu().numpy()
-    return h
 
 
 def _want(h, c, G0, size, halo):
