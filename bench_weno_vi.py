@@ -82,10 +82,11 @@ def torch_rule(torch, tdt, dev):
     return c4, w5f, r3
 
 
-def torch_rule_tendencies(torch, rule, ud, vd, wd, m, dzc, size, halo, outu, outv):
+def torch_rule_tendencies(torch, rule, ud, vd, wd, m, dzc, size, halo, outu, outv, w5v=None):
     """the rule of include/tripolar_hip_weno_vi.h as a host writes it in torch, on the parents ud, vd, wd, the metric planes m and dzc
     (Nz, 1, 1), into the interiors of the parents outu, outv: every line full 3-D elementwise passes, each product a temporary of its own;
-    the shared quantities are formed once, on whole planes"""
+    the shared quantities are formed once, on whole planes.  With `w5v` (bench_weno_vs.py): the rule of include/tripolar_hip_weno_vs.h, zr
+    is w5v(Z window, UB window, VB window)"""
     c4, w5f, r3 = rule
     (nx, ny, nz), (hx, hy, hz) = size, halo
     zs, ys, xs = slice(hz, hz + nz), slice(hy, hy + ny), slice(hx, hx + nx)
@@ -126,17 +127,21 @@ def torch_rule_tendencies(torch, rule, ud, vd, wd, m, dzc, size, halo, outu, out
     Q = lambda di, dj: M("dy_fc", di, dj) * W(ul, di, dj)
     vh = 0.5 * (0.5 * (P(-1, 0) + P(-1, 1)) + 0.5 * (P(0, 0) + P(0, 1)))
     vhat = vh / M("dx_fc")
+    UB = lambda di, dj: 0.5 * (W(ul, di, dj - 1) + W(ul, di, dj))
+    VB = lambda di, dj: 0.5 * (W(vl, di - 1, dj) + W(vl, di, dj))
+
+    def zr(pos, zw, nodes):
+        pick = lambda x: [torch.where(pos, x[n], x[5 - n]) for n in range(5)]
+        q = pick(zw)
+        return w5f(q, q) if w5v is None else w5v(q, pick([UB(di, dj) for di, dj in nodes]), pick([VB(di, dj) for di, dj in nodes]))
+
     zw = [Z(0, dj) for dj in range(-2, 4)]
-    pos = vhat >= 0
-    q = [torch.where(pos, zw[n], zw[5 - n]) for n in range(5)]
-    hu = -(vhat * w5f(q, q))
+    hu = -(vhat * zr(vhat >= 0, zw, [(0, dj) for dj in range(-2, 4)]))
     uh = 0.5 * (0.5 * (Q(0, -1) + Q(1, -1)) + 0.5 * (Q(0, 0) + Q(1, 0)))
     uhat = uh / M("dy_cf")
     zw = [Z(di, 0) for di in range(-2, 4)]
-    pos = uhat >= 0
-    q = [torch.where(pos, zw[n], zw[5 - n]) for n in range(5)]
-    hv = uhat * w5f(q, q)
-    del Zx, zw, q, pos, vh, uh, vhat, uhat
+    hv = uhat * zr(uhat >= 0, zw, [(di, 0) for di in range(-2, 4)])
+    del Zx, zw, vh, uh, vhat, uhat
     # the shared quantities of the new terms, on whole planes less one column and one row
     FX = (m["dy_fc"][None] * ul) * dzc
     FY = (m["dx_cf"][None] * vl) * dzc

@@ -65,7 +65,8 @@ def same_bits(x, y):
     return bool(((x.view(torch.int64) == y.view(torch.int64)) | (x.isnan() & y.isnan())).all())
 
 
-def main():
+def main(momentum_plan=osg.weno_vi_momentum_advection_plan):
+    """momentum_plan(u, v, w, Gu, Gv) -> the plan of Gu, Gv: examples/weno_vs_momentum_step.py passes the drivers' own scheme"""
     torch.cuda.set_device(0)
     underlying = osg.TripolarGrid(size=SIZE, halo=HALO, z=(-DEPTH, 0), first_pole_longitude=POLE_LON, north_poles_latitude=POLE_LAT)
     for name in ("dx_fc", "dy_fc", "az_fc", "az_ff"):             # the (Face, Center) / (Face, Face) nodes at the two grid poles have zero
@@ -88,7 +89,7 @@ def main():
     continuity = osg.continuity_plan(u, v, w)                      # fills w's halos by default
     continuity()
     tracer_tendency = osg.weno_tracer_advection_plan([c], u, v, w, [Gc])
-    momentum_tendency = osg.weno_vi_momentum_advection_plan(u, v, w, Gu, Gv)           # ONE call for Gu and Gv
+    momentum_tendency = momentum_plan(u, v, w, Gu, Gv)                                # ONE call for Gu and Gv
     ab2_tracer = osg.ab2_step_plan([c], [Gc], [Gc_prev], DT, fill_halos=True)
     ab2 = osg.ab2_velocity_step_plan(u, v, Gu, Gv, Gu_prev, Gv_prev, DT, GU=fs.GU, GV=fs.GV, fill_halos=True)
     mode = osg.barotropic_mode_plan(u, v, Ubar, Vbar)

@@ -42,5 +42,6 @@ from .weno_momentum import (DefaultStencil, EnergyConserving, EnstrophyConservin
 from .weno_xyz import WenoXyzTracerAdvectionPlan, weno_xyz_tracer_advection_plan, weno_xyz_tracer_advection_tendency
 from .weno_vi import (OnlySelfUpwinding, WenoViMomentumAdvectionPlan, weno_vi_momentum_advection_plan,
                       weno_vi_momentum_advection_tendency)
+from .weno_vs import WenoVsMomentumAdvectionPlan, weno_vs_momentum_advection_plan, weno_vs_momentum_advection_tendency
 
 __all__ = ["TripolarGrid", "ZipperBoundaryCondition"]

@@ -1,13 +1,13 @@
 """ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
 (include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency libraries (_advection.h,
-_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h).
+_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h, _weno_vs.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
 status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep,
-advection, momentum, weno, weno_momentum, weno_xyz and weno_vi.
+advection, momentum, weno, weno_momentum, weno_xyz, weno_vi and weno_vs.
 """
 import ctypes as C
 import os
@@ -192,6 +192,13 @@ WENO_VI_SIGNATURES = {
     "tpg_weno_vi_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_weno_vs.h declares (libtripolar_hip_weno_vs.so: the thirteenth library, no test build)
+WENO_VS_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno_vs.so")
+WENO_VS_SIGNATURES = {
+    "tpg_weno_vs_last_error": (C.c_char_p, []),
+    "tpg_weno_vs_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
+}
+
 
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
@@ -249,6 +256,8 @@ weno_xyz_lib, check_weno_xyz = _library("_weno_xyz", "WENO_XYZ_LIB_PATH", WENO_X
 WENO_TRACER_LIBRARIES = (weno_lib, weno_xyz_lib)                         # the two WENO schemes of the tracer tendency: centred in z, WENO in z
 # upwinding in every term of the velocity tendency.  Not in MOMENTUM_TENDENCY_LIBRARIES: its call takes dz_c where those two take dz_f
 weno_vi_lib, check_weno_vi = _library("_weno_vi", "WENO_VI_LIB_PATH", WENO_VI_SIGNATURES, "tpg_weno_vi_last_error")
+# the same call with VelocityStencil smoothness of the vorticity reconstruction: the drivers' WENOVectorInvariant(vorticity_order = 5)
+weno_vs_lib, check_weno_vs = _library("_weno_vs", "WENO_VS_LIB_PATH", WENO_VS_SIGNATURES, "tpg_weno_vs_last_error")
 
 
 def ft_of(dtype):

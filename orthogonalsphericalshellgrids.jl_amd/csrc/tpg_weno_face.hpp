@@ -57,6 +57,36 @@ __device__ __forceinline__ T weno_face_fs(T q0, T q1, T q2, T q3, T q4, T t0, T 
     return ((a0 * p0 + a1 * p1) + a2 * p2) / ((a0 + a1) + a2);
 }
 
+// W5V(q0..q4; a0..a4; b0..b4) of include/tripolar_hip_weno_vs.h (the VelocityStencil form of k_weno_momentum_advection,
+// tpg_weno_vorticity_kernel.hpp), the ONE definition: R above with each smoothness indicator the halved sum of the indicator of a0..a4 and
+// the indicator of b0..b4, the candidates p2, p1, p0 from q0..q4.  W5V(q; q; q) is R(q) bit for bit where x + x and T(0.5) * (2x) are exact
+// [recalled: Oceananigans' biased WENO weights for VelocityStencil -- the smoothness indicators of the tangential stencils of the two
+// velocities averaged onto (Face, Face), summed and halved (beta_sum); parity unpinned, like every operator here]
+template <typename T>
+__device__ __forceinline__ T weno_face_vs(T q0, T q1, T q2, T q3, T q4, T a0, T a1, T a2, T a3, T a4, T b0, T b1, T b2, T b3, T b4)
+{
+    constexpr T K13 = T(1) / T(3), K76 = T(7) / T(6), K116 = T(11) / T(6), K56 = T(5) / T(6), K16 = T(1) / T(6);
+    constexpr T K1312 = T(13) / T(12), K310 = T(3) / T(10), K35 = T(3) / T(5), K110 = T(1) / T(10);
+    constexpr T EPS = T(1e-8);
+    const T p2 = (K13 * q0 - K76 * q1) + K116 * q2;
+    const T p1 = (K56 * q2 - K16 * q1) + K13 * q3;
+    const T p0 = (K13 * q2 + K56 * q3) - K16 * q4;
+    const T sA2 = (a0 - T(2) * a1) + a2, dA2 = (a0 - T(4) * a1) + T(3) * a2;
+    const T sA1 = (a1 - T(2) * a2) + a3, dA1 = a1 - a3;
+    const T sA0 = (a2 - T(2) * a3) + a4, dA0 = (T(3) * a2 - T(4) * a3) + a4;
+    const T sB2 = (b0 - T(2) * b1) + b2, dB2 = (b0 - T(4) * b1) + T(3) * b2;
+    const T sB1 = (b1 - T(2) * b2) + b3, dB1 = b1 - b3;
+    const T sB0 = (b2 - T(2) * b3) + b4, dB0 = (T(3) * b2 - T(4) * b3) + b4;
+    const T bA2 = K1312 * (sA2 * sA2) + T(0.25) * (dA2 * dA2), bB2 = K1312 * (sB2 * sB2) + T(0.25) * (dB2 * dB2);
+    const T bA1 = K1312 * (sA1 * sA1) + T(0.25) * (dA1 * dA1), bB1 = K1312 * (sB1 * sB1) + T(0.25) * (dB1 * dB1);
+    const T bA0 = K1312 * (sA0 * sA0) + T(0.25) * (dA0 * dA0), bB0 = K1312 * (sB0 * sB0) + T(0.25) * (dB0 * dB0);
+    const T s2 = T(0.5) * (bA2 + bB2), s1 = T(0.5) * (bA1 + bB1), s0 = T(0.5) * (bA0 + bB0);
+    const T tau = abs_of(s0 - s2);
+    const T r0 = tau / (s0 + EPS), r1 = tau / (s1 + EPS), r2 = tau / (s2 + EPS);
+    const T w0 = K310 * (T(1) + r0 * r0), w1 = K35 * (T(1) + r1 * r1), w2 = K110 * (T(1) + r2 * r2);
+    return ((w0 * p0 + w1 * p1) + w2 * p2) / ((w0 + w1) + w2);
+}
+
 // R3(q0, q1, q2) of include/tripolar_hip_weno_xyz.h, the face value of order three: q1 is the upwind cell, q2 the downwind one
 template <typename T>
 __device__ __forceinline__ T weno_face3(T q0, T q1, T q2)

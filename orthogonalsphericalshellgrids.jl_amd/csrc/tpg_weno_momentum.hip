@@ -48,6 +48,7 @@ struct Switches {
     static constexpr bool SHARE = TPG_WMOM_SHARE;   // the Z beside the chunk come from the neighbouring lanes
     static constexpr bool NT = TPG_WMOM_NT;         // Gu, Gv go out in streaming stores
     static constexpr int WAVES = TPG_WMOM_WAVES;    // waves per SIMD the register allocation must leave room for (2: at most 256 VGPRs)
+    static constexpr bool VS = false;               // DefaultStencil smoothness: the built rule
 };
 
 }  // namespace

@@ -10,8 +10,9 @@
 // `if constexpr (FULL)` wraps what only the whole tendency needs: there is no run-time branch on the form, and the statements of the FULL
 // form are in the order they had before the two forms were one kernel.  The vorticity-only form has two `else` branches of its own, both
 // loads: dy_fc without az_cc, and the level's rows of u and v.  The including file passes its compile-time switches as a type SW
-// with SHARE (the Z beside the chunk come from the neighbouring lanes), NT (Gu, Gv go out in streaming stores) and WAVES (waves per SIMD
-// the register allocation must leave room for; 2: at most 256 VGPRs): each library keeps its own -D names and defaults.
+// with SHARE (the Z beside the chunk come from the neighbouring lanes), NT (Gu, Gv go out in streaming stores), WAVES (waves per SIMD
+// the register allocation must leave room for; 2: at most 256 VGPRs) and VS (the smoothness of the reconstruction is measured on the
+// velocities, below): each library keeps its own -D names and defaults.
 // W5 = weno_face (tpg_weno_face.hpp, the one definition): five selects on the sign (true for -0, false for NaN), ONE evaluation of W5 per
 // node and direction.  Evaluated in the field type T with no contraction; every operation is one correctly rounded IEEE operation.
 //
@@ -44,6 +45,18 @@
 // (profiles/weno_momentum/): 2 rows per item (1 row 11 % / 5 % slower, Float64 / Float32), no look-ahead ring (with 2 rows a ring of one level
 // spills; with 1 row it is slower than none), the shared Z (13 % / 2 % faster than every item forming its own), streaming stores (4 % / 3 %).
 // The vorticity-only form: profiles/vorticity_kernel/README.md.
+//
+// SW::VS (tpg_weno_vs.hip only, with !FULL only): the VelocityStencil form, the rule of include/tripolar_hip_weno_vs.h.  zr is W5V
+// (weno_face_vs, tpg_weno_face.hpp) of the same Z window and the windows of
+//     UB[i,j,k] = T(0.5) * (u[i,j-1,k] + u[i,j,k])   and   VB[i,j,k] = T(0.5) * (v[i-1,j,k] + v[i,j,k])
+// at the nodes of the Z: fifteen selects, ONE evaluation per node and direction.  Everything else is the form above, statement for statement.
+// [recalled: Oceananigans' biased WENO weights for VelocityStencil -- the smoothness indicators of the tangential stencils of the two
+// velocities averaged onto (Face, Face), summed and halved (beta_sum); parity unpinned, like every operator here]
+// - y.  UB and VB on the item's own columns at the rows -2 .. JT + 2 come from the rows of u and v the item holds for Z: no load is new.
+// - x.  UB and VB of the tile's rows on the columns -2, -1 and W .. W + 2 are the neighbouring lanes' own.  Every lane forms them itself
+//   from element loads (ub_at, vb_at: the same operations, the same bits, and exactly the elements of u and v that zeta_at reads for the Z
+//   of that node -- no address is new); with SW::SHARE_VS they are moved across lanes beside Z instead and only a lane at a wave edge, a
+//   row end or the seam forms them.  The loads won the A/B (5 % / 3 % of the call, Float64 / Float32): profiles/weno_vs/, with the resources.
 #pragma once
 #include "tpg_momentum_tendency.hpp"
 #include "tpg_weno_face.hpp"
@@ -60,6 +73,7 @@ template <typename T, int W, bool GEN, bool MASK, int JT, int LA, typename SW, b
 __global__ __launch_bounds__(256, SW::WAVES) void k_weno_momentum_advection(MomentumPtrs p, MomentumArgs a)
 {
     static_assert(FULL || !MASK, "the vorticity term alone is stored unmasked");
+    static_assert(!(FULL && SW::VS), "VelocityStencil smoothness is built for the vorticity term alone");
     typedef Chunk<T, W, GEN> cvec_t;
     constexpr int NR = JT + 2 * HALO;                              // rows -3 .. JT + 2
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,6 +217,15 @@ __global__ __launch_bounds__(256, SW::WAVES) void k_weno_momentum_advection(Mome
         const long long o = (long long)ro[r + HALO] + c, os = (long long)ro[r + HALO - 1] + c;
         return ((mdy[o] * vk[o] - mdy[o - 1] * vk[o - 1]) - (mdx[o] * uk[o] - mdx[os] * uk[os])) / maf[o];
     };
+    // UB and VB (SW::VS) at the node of that Z, from the elements of u and v zeta_at reads there: the same bits as a neighbouring item's own
+    auto ub_at = [&](const T* uk, int r, int c) -> T {
+        const long long o = (long long)ro[r + HALO] + c, os = (long long)ro[r + HALO - 1] + c;
+        return half * (uk[os] + uk[o]);
+    };
+    auto vb_at = [&](const T* vk, int r, int c) -> T {
+        const long long o = (long long)ro[r + HALO] + c;
+        return half * (vk[o - 1] + vk[o]);
+    };
 
     struct Level {
         T u[NR][W + 2], v[NR][W + 2];                              // this level: the cells around the chunk's rows (FULL: those rows are carried)
@@ -325,6 +348,43 @@ __global__ __launch_bounds__(256, SW::WAVES) void k_weno_momentum_advection(Mome
                         if (!(q < W ? east1_ok : east2_ok)) zx[r][W + 2 + q] = zeta_at(uk, vk, r, W + q);
                 }
             }
+            // SW::VS: UB and VB at the nodes of Z, indexed as Z and zx are
+            T UB[JT + 5][W], VB[JT + 5][W], ubx[JT][W + 5], vbx[JT][W + 5];
+            if constexpr (SW::VS) {
+                const T* uk = u + a.plane * k;
+                const T* vk = v + a.plane * k;
+#pragma unroll
+                for (int r = -2; r < JT + HALO; ++r)
+#pragma unroll
+                    for (int e = 0; e < W; ++e) {
+                        UB[r + 2][e] = half * (L.u[r + HALO - 1][e + 1] + L.u[r + HALO][e + 1]);
+                        VB[r + 2][e] = half * (L.v[r + HALO][e] + L.v[r + HALO][e + 1]);
+                    }
+#pragma unroll
+                for (int r = 0; r < JT; ++r) {
+#pragma unroll
+                    for (int e = 0; e < W; ++e) { ubx[r][e + 2] = UB[r + 2][e]; vbx[r][e + 2] = VB[r + 2][e]; }
+                    if constexpr (SW::SHARE_VS) {
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) {
+                            ubx[r][q] = __shfl_up(UB[r + 2][W - 2 + q], 1);
+                            vbx[r][q] = __shfl_up(VB[r + 2][W - 2 + q], 1);
+                        }
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) {
+                            ubx[r][W + 2 + q] = q < W ? __shfl_down(UB[r + 2][q % W], 1) : __shfl_down(UB[r + 2][q % W], 2);
+                            vbx[r][W + 2 + q] = q < W ? __shfl_down(VB[r + 2][q % W], 1) : __shfl_down(VB[r + 2][q % W], 2);
+                        }
+                    }
+                    if (!(SW::SHARE_VS && west_ok)) {
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) { ubx[r][q] = ub_at(uk, r, q - 2); vbx[r][q] = vb_at(vk, r, q - 2); }
+                    }
+#pragma unroll
+                    for (int q = 0; q < 3; ++q)
+                        if (!(SW::SHARE_VS && (q < W ? east1_ok : east2_ok))) { ubx[r][W + 2 + q] = ub_at(uk, r, W + q); vbx[r][W + 2 + q] = vb_at(vk, r, W + q); }
+                }
+            }
             // P: rows 0 .. JT, columns -1 .. W - 1.  Q: rows -1 .. JT - 1, columns 0 .. W.  K: rows -1 .. JT - 1, columns -1 .. W - 1, without (-1, -1)
             T P[JT + 1][W + 1], Q[JT + 1][W + 1], K[JT + 1][W + 1];
 #pragma unroll
@@ -348,8 +408,17 @@ __global__ __launch_bounds__(256, SW::WAVES) void k_weno_momentum_advection(Mome
                         const T vh = half * (half * (P[r][e] + P[r + 1][e]) + half * (P[r][e + 1] + P[r + 1][e + 1]));
                         const T vhat = vh / dxfc[r + HALO][e];
                         const bool pos = vhat >= T(0);             // true for -0, false for NaN
-                        const T zr = weno_face<T>(pos ? Z[r][e] : Z[r + 5][e], pos ? Z[r + 1][e] : Z[r + 4][e], pos ? Z[r + 2][e] : Z[r + 3][e],
-                                                  pos ? Z[r + 3][e] : Z[r + 2][e], pos ? Z[r + 4][e] : Z[r + 1][e]);     // Z[r + 2 + m][e]: Z[i, j + m]
+                        T zr;
+                        if constexpr (SW::VS)
+                            zr = weno_face_vs<T>(pos ? Z[r][e] : Z[r + 5][e], pos ? Z[r + 1][e] : Z[r + 4][e], pos ? Z[r + 2][e] : Z[r + 3][e],
+                                                 pos ? Z[r + 3][e] : Z[r + 2][e], pos ? Z[r + 4][e] : Z[r + 1][e],
+                                                 pos ? UB[r][e] : UB[r + 5][e], pos ? UB[r + 1][e] : UB[r + 4][e], pos ? UB[r + 2][e] : UB[r + 3][e],
+                                                 pos ? UB[r + 3][e] : UB[r + 2][e], pos ? UB[r + 4][e] : UB[r + 1][e],
+                                                 pos ? VB[r][e] : VB[r + 5][e], pos ? VB[r + 1][e] : VB[r + 4][e], pos ? VB[r + 2][e] : VB[r + 3][e],
+                                                 pos ? VB[r + 3][e] : VB[r + 2][e], pos ? VB[r + 4][e] : VB[r + 1][e]);
+                        else
+                            zr = weno_face<T>(pos ? Z[r][e] : Z[r + 5][e], pos ? Z[r + 1][e] : Z[r + 4][e], pos ? Z[r + 2][e] : Z[r + 3][e],
+                                              pos ? Z[r + 3][e] : Z[r + 2][e], pos ? Z[r + 4][e] : Z[r + 1][e]);     // Z[r + 2 + m][e]: Z[i, j + m]
                         const T hu = -(vhat * zr);
                         if constexpr (FULL) {
                             const T bu = (K[r + 1][e + 1] - K[r + 1][e]) / dxfc[r + HALO][e];
@@ -364,8 +433,17 @@ __global__ __launch_bounds__(256, SW::WAVES) void k_weno_momentum_advection(Mome
                         const T uh = half * (half * (Q[r][e] + Q[r][e + 1]) + half * (Q[r + 1][e] + Q[r + 1][e + 1]));
                         const T uhat = uh / dycf[r + HALO][e + 1];
                         const bool pos = uhat >= T(0);
-                        const T zr = weno_face<T>(pos ? zx[r][e] : zx[r][e + 5], pos ? zx[r][e + 1] : zx[r][e + 4], pos ? zx[r][e + 2] : zx[r][e + 3],
-                                                  pos ? zx[r][e + 3] : zx[r][e + 2], pos ? zx[r][e + 4] : zx[r][e + 1]);   // zx[r][e + 2 + m]: Z[i + m, j]
+                        T zr;
+                        if constexpr (SW::VS)
+                            zr = weno_face_vs<T>(pos ? zx[r][e] : zx[r][e + 5], pos ? zx[r][e + 1] : zx[r][e + 4], pos ? zx[r][e + 2] : zx[r][e + 3],
+                                                 pos ? zx[r][e + 3] : zx[r][e + 2], pos ? zx[r][e + 4] : zx[r][e + 1],
+                                                 pos ? ubx[r][e] : ubx[r][e + 5], pos ? ubx[r][e + 1] : ubx[r][e + 4], pos ? ubx[r][e + 2] : ubx[r][e + 3],
+                                                 pos ? ubx[r][e + 3] : ubx[r][e + 2], pos ? ubx[r][e + 4] : ubx[r][e + 1],
+                                                 pos ? vbx[r][e] : vbx[r][e + 5], pos ? vbx[r][e + 1] : vbx[r][e + 4], pos ? vbx[r][e + 2] : vbx[r][e + 3],
+                                                 pos ? vbx[r][e + 3] : vbx[r][e + 2], pos ? vbx[r][e + 4] : vbx[r][e + 1]);
+                        else
+                            zr = weno_face<T>(pos ? zx[r][e] : zx[r][e + 5], pos ? zx[r][e + 1] : zx[r][e + 4], pos ? zx[r][e + 2] : zx[r][e + 3],
+                                              pos ? zx[r][e + 3] : zx[r][e + 2], pos ? zx[r][e + 4] : zx[r][e + 1]);   // zx[r][e + 2 + m]: Z[i + m, j]
                         const T hv = uhat * zr;
                         if constexpr (FULL) {
                             const T bv = (K[r + 1][e + 1] - K[r][e + 1]) / dycf[r + HALO][e + 1];

@@ -19,7 +19,7 @@ of w are the caller's to fill first -- the rows Ny+1..Ny+3 are the Zipper's.  On
 spacings are z_center_spacings (dz_c); there is no dz_f in this call.  On an ImmersedBoundaryGrid the nodes k <= n_fc[i,j] of Gu and
 k <= n_cf[i,j] of Gv get 0 inside the call, and everything is computed unmasked.
 
-Stays out: VelocityStencil smoothness, other orders, Oceananigans' drop of the order beside the south wall and immersed nodes,
+Stays out: VelocityStencil smoothness (weno_vs.py builds it, as a call of its own), other orders, Oceananigans' drop of the order beside the south wall and immersed nodes,
 latitude bands, the Julia hooks.
 
 The plan form holds its tensors: calling it enqueues on torch's current stream and allocates nothing (usable inside torch.cuda.graph)."""
