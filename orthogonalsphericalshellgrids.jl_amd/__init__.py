@@ -43,5 +43,7 @@ from .weno_xyz import WenoXyzTracerAdvectionPlan, weno_xyz_tracer_advection_plan
 from .weno_vi import (OnlySelfUpwinding, WenoViMomentumAdvectionPlan, weno_vi_momentum_advection_plan,
                       weno_vi_momentum_advection_tendency)
 from .weno_vs import WenoVsMomentumAdvectionPlan, weno_vs_momentum_advection_plan, weno_vs_momentum_advection_tendency
+from .hydrostatic import (BuoyancyTracer, HydrostaticPressurePlan, HydrostaticSphericalCoriolis, HydrostaticTendenciesPlan,
+                          coriolis_parameter, hydrostatic_tendencies, hydrostatic_tendencies_plan, update_hydrostatic_pressure)
 
-__all__ = ["TripolarGrid", "ZipperBoundaryCondition"]
+__all__ =["TripolarGrid", "ZipperBoundaryCondition"]

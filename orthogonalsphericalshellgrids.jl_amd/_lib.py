@@ -1,13 +1,13 @@
 """ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
 (include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency libraries (_advection.h,
-_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h, _weno_vs.h).
+_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h, _weno_vs.h, _hydrostatic.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
 status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep,
-advection, momentum, weno, weno_momentum, weno_xyz, weno_vi and weno_vs.
+advection, momentum, weno, weno_momentum, weno_xyz, weno_vi, weno_vs and hydrostatic.
 """
 import ctypes as C
 import os
@@ -199,6 +199,15 @@ WENO_VS_SIGNATURES = {
     "tpg_weno_vs_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_hydrostatic.h declares (libtripolar_hip_hydrostatic.so: the fourteenth library, no test build)
+HYDROSTATIC_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_hydrostatic.so")
+TPG_CORIOLIS_ENSTROPHY_CONSERVING, TPG_CORIOLIS_ENERGY_CONSERVING = 0, 1     # `coriolis_scheme` of tpg_hydrostatic_tendencies
+TPG_TENDENCY_ADD, TPG_TENDENCY_WRITE = 0, 1                                  # its `mode`
+HYDROSTATIC_SIGNATURES = {
+    "tpg_hydrostatic_last_error": (C.c_char_p, []),
+    "tpg_hydrostatic_tendencies": (_i, [_vp] * 14 + [C.c_double, _i, _i] + _geom + [_i, _vp]),
+}
+
 
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
@@ -258,6 +267,8 @@ WENO_TRACER_LIBRARIES = (weno_lib, weno_xyz_lib)                         # the t
 weno_vi_lib, check_weno_vi = _library("_weno_vi", "WENO_VI_LIB_PATH", WENO_VI_SIGNATURES, "tpg_weno_vi_last_error")
 # the same call with VelocityStencil smoothness of the vorticity reconstruction: the drivers' WENOVectorInvariant(vorticity_order = 5)
 weno_vs_lib, check_weno_vs = _library("_weno_vs", "WENO_VS_LIB_PATH", WENO_VS_SIGNATURES, "tpg_weno_vs_last_error")
+# the Coriolis and hydrostatic pressure-gradient tendencies, accumulated into what an advection call left in Gu, Gv
+hydrostatic_lib, check_hydrostatic = _library("_hydrostatic", "HYDROSTATIC_LIB_PATH", HYDROSTATIC_SIGNATURES, "tpg_hydrostatic_last_error")
 
 
 def ft_of(dtype):
