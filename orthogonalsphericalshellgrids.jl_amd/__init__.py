@@ -45,5 +45,8 @@ from .weno_vi import (OnlySelfUpwinding, WenoViMomentumAdvectionPlan, weno_vi_mo
 from .weno_vs import WenoVsMomentumAdvectionPlan, weno_vs_momentum_advection_plan, weno_vs_momentum_advection_tendency
 from .hydrostatic import (BuoyancyTracer, HydrostaticPressurePlan, HydrostaticSphericalCoriolis, HydrostaticTendenciesPlan,
                           coriolis_parameter, hydrostatic_tendencies, hydrostatic_tendencies_plan, update_hydrostatic_pressure)
+from .vertical_diffusion import (ExplicitTimeDiscretization, ImplicitStepPlan, VerticalImplicitDiffusionPlan, VerticalScalarDiffusivity,
+                                 VerticallyImplicitTimeDiscretization, implicit_step_plan, vertical_implicit_diffusion,
+                                 vertical_implicit_diffusion_plan)
 
 __all__ =["TripolarGrid", "ZipperBoundaryCondition"]

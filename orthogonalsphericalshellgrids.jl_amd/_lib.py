@@ -1,13 +1,13 @@
 """ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
 (include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency libraries (_advection.h,
-_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h, _weno_vs.h, _hydrostatic.h).
+_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h, _weno_vs.h, _hydrostatic.h, _vertical_diffusion.h).
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
 A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
 status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep,
-advection, momentum, weno, weno_momentum, weno_xyz, weno_vi, weno_vs and hydrostatic.
+advection, momentum, weno, weno_momentum, weno_xyz, weno_vi, weno_vs, hydrostatic and vertical_diffusion.
 """
 import ctypes as C
 import os
@@ -208,6 +208,16 @@ HYDROSTATIC_SIGNATURES = {
     "tpg_hydrostatic_tendencies": (_i, [_vp] * 14 + [C.c_double, _i, _i] + _geom + [_i, _vp]),
 }
 
+# every symbol include/tripolar_hip_vertical_diffusion.h declares (libtripolar_hip_vertical_diffusion.so: the fifteenth library, no test build)
+VERTICAL_DIFFUSION_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_vertical_diffusion.so")
+TPG_KAPPA_CONSTANT, TPG_KAPPA_PROFILE, TPG_KAPPA_FIELD = 0, 1, 2             # `kappa_form` of tpg_vertical_implicit_diffusion
+TPG_VDIFF_AUTO, TPG_VDIFF_ON_CHIP, TPG_VDIFF_STREAMED = 0, 1, 2              # its `path`
+VERTICAL_DIFFUSION_SIGNATURES = {
+    "tpg_vertical_diffusion_last_error": (C.c_char_p, []),
+    "tpg_vertical_diffusion_on_chip_levels": (_i, [_i, _i]),
+    "tpg_vertical_implicit_diffusion": (_i, [C.POINTER(_vp), _i, _vp, C.c_double, _i, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _i] + _geom + [_i, _vp]),
+}
+
 
 def bind(path, signatures):
     """dlopen `path` and declare `signatures` on it (AttributeError if the ABI is incomplete)"""
@@ -269,6 +279,9 @@ weno_vi_lib, check_weno_vi = _library("_weno_vi", "WENO_VI_LIB_PATH", WENO_VI_SI
 weno_vs_lib, check_weno_vs = _library("_weno_vs", "WENO_VS_LIB_PATH", WENO_VS_SIGNATURES, "tpg_weno_vs_last_error")
 # the Coriolis and hydrostatic pressure-gradient tendencies, accumulated into what an advection call left in Gu, Gv
 hydrostatic_lib, check_hydrostatic = _library("_hydrostatic", "HYDROSTATIC_LIB_PATH", HYDROSTATIC_SIGNATURES, "tpg_hydrostatic_last_error")
+# the vertically implicit diffusion step: the column solve after the AB2 update of u, v and the tracers
+vertical_diffusion_lib, check_vertical_diffusion = _library("_vertical_diffusion", "VERTICAL_DIFFUSION_LIB_PATH", VERTICAL_DIFFUSION_SIGNATURES,
+                                                            "tpg_vertical_diffusion_last_error")
 
 
 def ft_of(dtype):
