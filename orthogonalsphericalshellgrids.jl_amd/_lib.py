@@ -1,14 +1,16 @@
-"""ctypes binding of libtripolar_hip.so (include/tripolar_hip.h), of the five operator libraries beside it
-(include/tripolar_hip_operators.h, _continuity.h, _barotropic.h, _free_surface.h, _timestep.h) and of the tendency libraries (_advection.h,
-_momentum.h, _weno.h, _weno_momentum.h, _weno_xyz.h, _weno_vi.h, _weno_vs.h, _hydrostatic.h, _vertical_diffusion.h).
+"""ctypes binding of the shared libraries of the package: the product, libtripolar_hip.so (include/tripolar_hip.h), and the operator libraries.
 
 This is the ONLY compute backend of the package: if a shared library is missing or a call
 fails, the caller gets an exception -- there is no CPU or PyTorch fallback by design.
 
-A library is described once -- its path, its signature table, its *_last_error symbol -- and _library() makes its loader and its
-status checker from that: lib / check, operators_lib / check_operators, and so on for continuity, barotropic, free_surface, timestep,
-advection, momentum, weno, weno_momentum, weno_xyz, weno_vi, weno_vs, hydrostatic and vertical_diffusion.
+The convention, stated once: the operator library <name> is libtripolar_hip_<name>.so beside this file, built from csrc/tpg_<name>.hip through
+csrc/<name>.map (csrc/Makefile lists the names), it exports what include/tripolar_hip_<name>.h declares, and its error channel is
+tpg_<name>_last_error.  Here it is one table <NAME>_SIGNATURES of every symbol that header declares, (restype, argtypes) each, and one line
+<name>_lib, check_<name> = _library("<name>", <NAME>_SIGNATURES), which makes its loader and its status checker, sets <NAME>_LIB_PATH and
+enters a record in LIBRARIES, the registry of every library in the order of definition: what build() loads and tests/test_library_table.py
+checks against the headers, the maps and the built files.
 """
+import collections
 import ctypes as C
 import os
 
@@ -57,7 +59,7 @@ class TripolarHipError(RuntimeError):
         self.status = status
 
 
-# every symbol include/tripolar_hip.h declares: (restype, argtypes)
+# the product: every symbol include/tripolar_hip.h declares, (restype, argtypes)
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
 _geom = [_i] * 6
 SIGNATURES = {
@@ -110,37 +112,28 @@ SIGNATURES = {
     "tpg_convert_frame": (_i, [_vp] * 8 + [_i] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_operators.h declares (libtripolar_hip_operators.so: a library of its own beside the product's)
-OPERATORS_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_operators.so")
-OPERATOR_SIGNATURES = {
+# the operator libraries, <NAME>_SIGNATURES each: every symbol include/tripolar_hip_<name>.h declares
+OPERATORS_SIGNATURES = {
     "tpg_operators_last_error": (C.c_char_p, []),
     "tpg_vertical_vorticity": (_i, [_vp] * 7 + [C.c_double] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_continuity.h declares (libtripolar_hip_continuity.so: the third library, no test build)
-CONTINUITY_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_continuity.so")
 CONTINUITY_SIGNATURES = {
     "tpg_continuity_last_error": (C.c_char_p, []),
     "tpg_w_from_continuity": (_i, [_vp] * 9 + [C.c_double] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_barotropic.h declares (libtripolar_hip_barotropic.so: the fourth library, no test build)
-BAROTROPIC_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_barotropic.so")
 BAROTROPIC_SIGNATURES = {
     "tpg_barotropic_last_error": (C.c_char_p, []),
     "tpg_barotropic_mode": (_i, [_vp] * 5 + _geom + [_i, _i, _vp]),
     "tpg_barotropic_correction": (_i, [_vp] * 9 + [C.c_double] + _geom + [_i, _i, _vp]),
 }
 
-# every symbol include/tripolar_hip_free_surface.h declares (libtripolar_hip_free_surface.so: the fifth library, no test build)
-FREE_SURFACE_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_free_surface.so")
 FREE_SURFACE_SIGNATURES = {
     "tpg_free_surface_last_error": (C.c_char_p, []),
     "tpg_free_surface_substep": (_i, [_vp] * 19 + [C.c_double] * 3 + [_i] * 6 + [_vp]),
 }
 
-# every symbol include/tripolar_hip_timestep.h declares (libtripolar_hip_timestep.so: the sixth library, no test build)
-TIMESTEP_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_timestep.so")
 TPG_AB2_EULER, TPG_AB2_STORE_PREVIOUS = 1, 2                 # flag bits of both calls
 TIMESTEP_SIGNATURES = {
     "tpg_timestep_last_error": (C.c_char_p, []),
@@ -148,59 +141,43 @@ TIMESTEP_SIGNATURES = {
     "tpg_ab2_step_fields": (_i, [C.POINTER(_vp)] * 3 + [_i] + [C.c_double] * 2 + [_i] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_advection.h declares (libtripolar_hip_advection.so: the seventh library, no test build)
-ADVECTION_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_advection.so")
 TPG_ADVECTION_CENTERED2 = 0                                  # `scheme` of tpg_tracer_advection_tendency: the only one built
 ADVECTION_SIGNATURES = {
     "tpg_advection_last_error": (C.c_char_p, []),
     "tpg_tracer_advection_tendency": (_i, [C.POINTER(_vp)] * 2 + [_i] + [_vp] * 8 + [C.c_double, _i] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_momentum.h declares (libtripolar_hip_momentum.so: the eighth library, no test build)
-MOMENTUM_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_momentum.so")
 TPG_MOMENTUM_ENSTROPHY_CONSERVING = 0                        # `scheme` of tpg_momentum_advection_tendency: the only one built
 MOMENTUM_SIGNATURES = {
     "tpg_momentum_last_error": (C.c_char_p, []),
     "tpg_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double, _i] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_weno.h declares (libtripolar_hip_weno.so: the ninth library, no test build)
-WENO_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno.so")
 WENO_SIGNATURES = {
     "tpg_weno_last_error": (C.c_char_p, []),
     "tpg_weno_tracer_advection_tendency": (_i, [C.POINTER(_vp)] * 2 + [_i] + [_vp] * 8 + [C.c_double] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_weno_momentum.h declares (libtripolar_hip_weno_momentum.so: the tenth library, no test build)
-WENO_MOMENTUM_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno_momentum.so")
 WENO_MOMENTUM_SIGNATURES = {
     "tpg_weno_momentum_last_error": (C.c_char_p, []),
     "tpg_weno_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_weno_xyz.h declares (libtripolar_hip_weno_xyz.so: the eleventh library, no test build)
-WENO_XYZ_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno_xyz.so")
 WENO_XYZ_SIGNATURES = {
     "tpg_weno_xyz_last_error": (C.c_char_p, []),
     "tpg_weno_xyz_tracer_advection_tendency": (_i, [C.POINTER(_vp)] * 2 + [_i] + [_vp] * 8 + [C.c_double] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_weno_vi.h declares (libtripolar_hip_weno_vi.so: the twelfth library, no test build)
-WENO_VI_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno_vi.so")
 WENO_VI_SIGNATURES = {
     "tpg_weno_vi_last_error": (C.c_char_p, []),
     "tpg_weno_vi_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_weno_vs.h declares (libtripolar_hip_weno_vs.so: the thirteenth library, no test build)
-WENO_VS_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_weno_vs.so")
 WENO_VS_SIGNATURES = {
     "tpg_weno_vs_last_error": (C.c_char_p, []),
     "tpg_weno_vs_momentum_advection_tendency": (_i, [_vp] * 16 + [C.c_double] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_hydrostatic.h declares (libtripolar_hip_hydrostatic.so: the fourteenth library, no test build)
-HYDROSTATIC_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_hydrostatic.so")
 TPG_CORIOLIS_ENSTROPHY_CONSERVING, TPG_CORIOLIS_ENERGY_CONSERVING = 0, 1     # `coriolis_scheme` of tpg_hydrostatic_tendencies
 TPG_TENDENCY_ADD, TPG_TENDENCY_WRITE = 0, 1                                  # its `mode`
 HYDROSTATIC_SIGNATURES = {
@@ -208,8 +185,6 @@ HYDROSTATIC_SIGNATURES = {
     "tpg_hydrostatic_tendencies": (_i, [_vp] * 14 + [C.c_double, _i, _i] + _geom + [_i, _vp]),
 }
 
-# every symbol include/tripolar_hip_vertical_diffusion.h declares (libtripolar_hip_vertical_diffusion.so: the fifteenth library, no test build)
-VERTICAL_DIFFUSION_LIB_PATH = os.path.join(_HERE, "libtripolar_hip_vertical_diffusion.so")
 TPG_KAPPA_CONSTANT, TPG_KAPPA_PROFILE, TPG_KAPPA_FIELD = 0, 1, 2             # `kappa_form` of tpg_vertical_implicit_diffusion
 TPG_VDIFF_AUTO, TPG_VDIFF_ON_CHIP, TPG_VDIFF_STREAMED = 0, 1, 2              # its `path`
 VERTICAL_DIFFUSION_SIGNATURES = {
@@ -238,11 +213,19 @@ def _load(path, signatures):
     return bind(path, signatures)
 
 
-def _library(handle, path, signatures, last_error):
-    """(loader, checker) of one library.  `handle` and `path` NAME module-level variables, read at every call: the cached handle (None: not
-    loaded yet; tools.testlib swaps _lib) and the path, which a caller may assign before the first load.  `last_error`: its error channel."""
+# one record of LIBRARIES: the file names under include/ and csrc/, the NAME of the module-level variable that holds the path, the table, the two functions
+Library = collections.namedtuple("Library", "header map path_global signatures load check")
+LIBRARIES = {}
+
+
+def _library(name, signatures, handle=None, path=None, last_error=None, header=None, map=None):
+    """(loader, checker) of the library `name`, entered in LIBRARIES.  Everything else follows from the name (see the module docstring); only the
+    product spells it out.  `handle` and `path` NAME module-level variables, read at every call: the cached handle (None: not loaded yet;
+    tools.testlib swaps _lib) and the path, which a caller may assign before the first load.  `last_error`: its error channel."""
+    handle, path, last_error = handle or f"_{name}", path or f"{name.upper()}_LIB_PATH", last_error or f"tpg_{name}_last_error"
     g = globals()
     g.setdefault(handle, None)
+    g.setdefault(path, os.path.join(_HERE, f"libtripolar_hip_{name}.so"))
 
     def load():
         if g[handle] is None:
@@ -254,34 +237,25 @@ def _library(handle, path, signatures, last_error):
             raise TripolarHipError(status, getattr(load(), last_error)().decode("utf-8", "replace"))
 
     load.__doc__ = f"Load the library at {path} (once); ImportError if it has not been built."
+    LIBRARIES[name] = Library(header or f"tripolar_hip_{name}.h", map or f"{name}.map", path, signatures, load, check)
     return load, check
 
 
-lib, check = _library("_lib", "LIB_PATH", SIGNATURES, "tpg_last_error")
-operators_lib, check_operators = _library("_operators", "OPERATORS_LIB_PATH", OPERATOR_SIGNATURES, "tpg_operators_last_error")
-continuity_lib, check_continuity = _library("_continuity", "CONTINUITY_LIB_PATH", CONTINUITY_SIGNATURES, "tpg_continuity_last_error")
-barotropic_lib, check_barotropic = _library("_barotropic", "BAROTROPIC_LIB_PATH", BAROTROPIC_SIGNATURES, "tpg_barotropic_last_error")
-free_surface_lib, check_free_surface = _library("_free_surface", "FREE_SURFACE_LIB_PATH", FREE_SURFACE_SIGNATURES, "tpg_free_surface_last_error")
-timestep_lib, check_timestep = _library("_timestep", "TIMESTEP_LIB_PATH", TIMESTEP_SIGNATURES, "tpg_timestep_last_error")
-advection_lib, check_advection = _library("_advection", "ADVECTION_LIB_PATH", ADVECTION_SIGNATURES, "tpg_advection_last_error")
-OPERATOR_LIBRARIES = (operators_lib, continuity_lib, barotropic_lib, free_surface_lib, timestep_lib)
-momentum_lib, check_momentum = _library("_momentum", "MOMENTUM_LIB_PATH", MOMENTUM_SIGNATURES, "tpg_momentum_last_error")
-weno_lib, check_weno = _library("_weno", "WENO_LIB_PATH", WENO_SIGNATURES, "tpg_weno_last_error")
-TENDENCY_LIBRARIES = (advection_lib, momentum_lib, weno_lib)             # what produces the tendencies the AB2 step consumes
-weno_momentum_lib, check_weno_momentum = _library("_weno_momentum", "WENO_MOMENTUM_LIB_PATH", WENO_MOMENTUM_SIGNATURES,
-                                                  "tpg_weno_momentum_last_error")
-MOMENTUM_TENDENCY_LIBRARIES = (momentum_lib, weno_momentum_lib)          # the two vorticity schemes of the velocity tendencies
-weno_xyz_lib, check_weno_xyz = _library("_weno_xyz", "WENO_XYZ_LIB_PATH", WENO_XYZ_SIGNATURES, "tpg_weno_xyz_last_error")
-WENO_TRACER_LIBRARIES = (weno_lib, weno_xyz_lib)                         # the two WENO schemes of the tracer tendency: centred in z, WENO in z
-# upwinding in every term of the velocity tendency.  Not in MOMENTUM_TENDENCY_LIBRARIES: its call takes dz_c where those two take dz_f
-weno_vi_lib, check_weno_vi = _library("_weno_vi", "WENO_VI_LIB_PATH", WENO_VI_SIGNATURES, "tpg_weno_vi_last_error")
-# the same call with VelocityStencil smoothness of the vorticity reconstruction: the drivers' WENOVectorInvariant(vorticity_order = 5)
-weno_vs_lib, check_weno_vs = _library("_weno_vs", "WENO_VS_LIB_PATH", WENO_VS_SIGNATURES, "tpg_weno_vs_last_error")
-# the Coriolis and hydrostatic pressure-gradient tendencies, accumulated into what an advection call left in Gu, Gv
-hydrostatic_lib, check_hydrostatic = _library("_hydrostatic", "HYDROSTATIC_LIB_PATH", HYDROSTATIC_SIGNATURES, "tpg_hydrostatic_last_error")
-# the vertically implicit diffusion step: the column solve after the AB2 update of u, v and the tracers
-vertical_diffusion_lib, check_vertical_diffusion = _library("_vertical_diffusion", "VERTICAL_DIFFUSION_LIB_PATH", VERTICAL_DIFFUSION_SIGNATURES,
-                                                            "tpg_vertical_diffusion_last_error")
+lib, check = _library("product", SIGNATURES, handle="_lib", path="LIB_PATH", last_error="tpg_last_error", header="tripolar_hip.h", map="exports.map")
+operators_lib, check_operators = _library("operators", OPERATORS_SIGNATURES)
+continuity_lib, check_continuity = _library("continuity", CONTINUITY_SIGNATURES)
+barotropic_lib, check_barotropic = _library("barotropic", BAROTROPIC_SIGNATURES)
+free_surface_lib, check_free_surface = _library("free_surface", FREE_SURFACE_SIGNATURES)
+timestep_lib, check_timestep = _library("timestep", TIMESTEP_SIGNATURES)
+advection_lib, check_advection = _library("advection", ADVECTION_SIGNATURES)
+momentum_lib, check_momentum = _library("momentum", MOMENTUM_SIGNATURES)
+weno_lib, check_weno = _library("weno", WENO_SIGNATURES)
+weno_momentum_lib, check_weno_momentum = _library("weno_momentum", WENO_MOMENTUM_SIGNATURES)
+weno_xyz_lib, check_weno_xyz = _library("weno_xyz", WENO_XYZ_SIGNATURES)
+weno_vi_lib, check_weno_vi = _library("weno_vi", WENO_VI_SIGNATURES)
+weno_vs_lib, check_weno_vs = _library("weno_vs", WENO_VS_SIGNATURES)
+hydrostatic_lib, check_hydrostatic = _library("hydrostatic", HYDROSTATIC_SIGNATURES)
+vertical_diffusion_lib, check_vertical_diffusion = _library("vertical_diffusion", VERTICAL_DIFFUSION_SIGNATURES)
 
 
 def ft_of(dtype):

@@ -2,8 +2,6 @@
 and tpg_ab2_step_fields (status and message; every call below fails in validation, none reaches a launch, the pointers are fabricated and
 never dereferenced), every refusal of the Python layer on host-only grid records, and with_dt."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
@@ -33,23 +31,10 @@ def _vel(lib, p, geom=G, Hy2=HY2, ft=1, flags=STORE, dt=0.5, chi=0.1):
     return lib.tpg_ab2_step_velocities(*(p[k] for k in ARGS), dt, chi, flags, *geom, Hy2, ft, None)
 
 
-def test_header_exports_and_signatures_are_the_three_names(osg, tmp_path):
-    from test_abi import ROOT, declared_symbols, exported_symbols
+def test_header_exports_and_signatures_are_the_three_names(osg):
+    from test_abi import declared_symbols, exported_symbols
     osg._lib.timestep_lib()
     assert declared_symbols("tripolar_hip_timestep.h") == NAMES == exported_symbols(osg._lib.TIMESTEP_LIB_PATH) == sorted(osg._lib.TIMESTEP_SIGNATURES)
-    for other in (osg._lib.LIB_PATH, osg._lib.OPERATORS_LIB_PATH, osg._lib.CONTINUITY_LIB_PATH, osg._lib.BAROTROPIC_LIB_PATH,
-                  osg._lib.FREE_SURFACE_LIB_PATH):
-        assert not set(NAMES) & set(exported_symbols(other))
-    assert osg._lib.timestep_lib in osg._lib.OPERATOR_LIBRARIES and len(osg._lib.OPERATOR_LIBRARIES) == 5
-    und = subprocess.run(["nm", "-D", "--undefined-only", osg._lib.TIMESTEP_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "getenv" not in und                                     # reads no environment variable
-    src = tmp_path / "abi.c"
-    src.write_text('#include "tripolar_hip_timestep.h"\ntypedef void (*fn)(void);\nstatic fn table[] = {' + ", ".join(f"(fn){n}" for n in NAMES)
-                   + "};\nint main(void) { return sizeof(table) == 0 || TPG_AB2_EULER != 1 || TPG_AB2_STORE_PREVIOUS != 2; }\n")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "abi.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert (osg._lib.TPG_AB2_EULER, osg._lib.TPG_AB2_STORE_PREVIOUS) == (EULER, STORE)
 
 
 def test_velocity_argument_errors_without_device_work(osg):

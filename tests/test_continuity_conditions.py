@@ -1,7 +1,6 @@
 """Host-side tests of w from continuity and the horizontal divergence (no GPU): the export list of libtripolar_hip_continuity.so, every
 argument error of tpg_w_from_continuity (status and message; every call below fails in validation, none reaches a launch, the pointers are
 never dereferenced), the argument checks of the Python layer and z_center_spacings."""
-import subprocess
 
 import pytest
 
@@ -9,13 +8,9 @@ import pytest
 def test_argument_errors_without_device_work(osg):
     from test_abi import declared_symbols, exported_symbols
     lib = osg._lib.continuity_lib()
-    # header = exports = signatures; the new symbols are in neither of the other two libraries
+    # header = exports = signatures
     names = declared_symbols("tripolar_hip_continuity.h")
     assert names == ["tpg_continuity_last_error", "tpg_w_from_continuity"] == exported_symbols(osg._lib.CONTINUITY_LIB_PATH) == sorted(osg._lib.CONTINUITY_SIGNATURES)
-    for other in (osg._lib.LIB_PATH, osg._lib.OPERATORS_LIB_PATH):
-        assert not set(names) & set(exported_symbols(other))
-    und = subprocess.run(["nm", "-D", "--undefined-only", osg._lib.CONTINUITY_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "getenv" not in und                                     # reads no environment variable
     err = lambda: lib.tpg_continuity_last_error().decode()
     call = lambda *a: lib.tpg_w_from_continuity(*a)
     g = (48, 40, 3, 4, 4, 4)

@@ -2,8 +2,6 @@
 error of tpg_free_surface_substep (status and message; every call below fails in validation, none reaches a launch, the pointers are
 fabricated and never dereferenced), every refusal of the Python layer on host-only grid records, and the ping-pong bookkeeping of the
 sub-cycle for odd and even sub-step counts."""
-import os
-import subprocess
 
 import pytest
 
@@ -29,20 +27,10 @@ def _call(lib, p, geom=(NX, NY, NZ, HX, HY2), ft=1):
     return lib.tpg_free_surface_substep(*(p[k] for k in ARGS), 0.5, 9.8, 0.1, *geom, ft, None)
 
 
-def test_header_exports_and_signatures_are_the_two_names(osg, tmp_path):
-    from test_abi import ROOT, declared_symbols, exported_symbols
+def test_header_exports_and_signatures_are_the_two_names(osg):
+    from test_abi import declared_symbols, exported_symbols
     osg._lib.free_surface_lib()
     assert declared_symbols("tripolar_hip_free_surface.h") == NAMES == exported_symbols(osg._lib.FREE_SURFACE_LIB_PATH) == sorted(osg._lib.FREE_SURFACE_SIGNATURES)
-    for other in (osg._lib.LIB_PATH, osg._lib.OPERATORS_LIB_PATH, osg._lib.CONTINUITY_LIB_PATH, osg._lib.BAROTROPIC_LIB_PATH):
-        assert not set(NAMES) & set(exported_symbols(other))
-    und = subprocess.run(["nm", "-D", "--undefined-only", osg._lib.FREE_SURFACE_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "getenv" not in und                                     # reads no environment variable
-    src = tmp_path / "abi.c"
-    src.write_text('#include "tripolar_hip_free_surface.h"\ntypedef void (*fn)(void);\nstatic fn table[] = {' + ", ".join(f"(fn){n}" for n in NAMES)
-                   + "};\nint main(void) { return sizeof(table) == 0; }\n")
-    r = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src),
-                        "-o", str(tmp_path / "abi.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
 
 
 def test_substep_argument_errors_without_device_work(osg):

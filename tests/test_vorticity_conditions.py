@@ -1,6 +1,5 @@
 """Host-side tests of the vertical vorticity (no GPU): every argument error of tpg_vertical_vorticity (status and message; every call below
 fails in validation, none reaches a launch, the pointers are never dereferenced) and the argument checks of the Python layer."""
-import subprocess
 
 import pytest
 
@@ -10,12 +9,10 @@ def test_argument_errors_without_device_work(osg):
     lib = osg._lib.operators_lib()
     # header = exports = signatures, for the operators library as for the product's; the test build adds the knob reload and nothing else
     names = declared_symbols("tripolar_hip_operators.h")
-    assert names == ["tpg_operators_last_error", "tpg_vertical_vorticity"] == exported_symbols(osg._lib.OPERATORS_LIB_PATH) == sorted(osg._lib.OPERATOR_SIGNATURES)
+    assert names == ["tpg_operators_last_error", "tpg_vertical_vorticity"] == exported_symbols(osg._lib.OPERATORS_LIB_PATH) == sorted(osg._lib.OPERATORS_SIGNATURES)
     from tools import testlib
     assert exported_symbols(testlib.OPERATORS_LIB_PATH) == sorted(names + ["tpg_reload_config"])
     assert "tpg_vertical_vorticity" not in exported_symbols(osg._lib.LIB_PATH) and osg._lib.lib().tpg_version() == 600
-    und = subprocess.run(["nm", "-D", "--undefined-only", osg._lib.OPERATORS_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert "getenv" not in und                                     # the product build reads no environment variable
     err = lambda: lib.tpg_operators_last_error().decode()
     call = lambda *a: lib.tpg_vertical_vorticity(*a)
     g = (48, 40, 3, 4, 4, 4)

@@ -44,7 +44,7 @@ def operators_lib():
     if _operators is None:
         if not os.path.exists(OPERATORS_LIB_PATH):
             raise ImportError(f"{OPERATORS_LIB_PATH} not found: build it with `make -C orthogonalsphericalshellgrids.jl_amd/csrc`")
-        _operators = product.bind(OPERATORS_LIB_PATH, {**product.OPERATOR_SIGNATURES, "tpg_reload_config": (_i, [])})
+        _operators = product.bind(OPERATORS_LIB_PATH, {**product.OPERATORS_SIGNATURES, "tpg_reload_config": (_i, [])})
     return _operators
 
 
