@@ -48,5 +48,6 @@ from .hydrostatic import (BuoyancyTracer, HydrostaticPressurePlan, HydrostaticSp
 from .vertical_diffusion import (ExplicitTimeDiscretization, ImplicitStepPlan, VerticalImplicitDiffusionPlan, VerticalScalarDiffusivity,
                                  VerticallyImplicitTimeDiscretization, implicit_step_plan, vertical_implicit_diffusion,
                                  vertical_implicit_diffusion_plan)
+from .diffusion import DiffusiveTendencyPlan, HorizontalScalarDiffusivity, diffusive_tendency, diffusive_tendency_plan
 
 __all__ =["TripolarGrid", "ZipperBoundaryCondition"]
