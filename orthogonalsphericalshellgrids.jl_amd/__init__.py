@@ -49,5 +49,8 @@ from .vertical_diffusion import (ExplicitTimeDiscretization, ImplicitStepPlan, V
                                  VerticallyImplicitTimeDiscretization, implicit_step_plan, vertical_implicit_diffusion,
                                  vertical_implicit_diffusion_plan)
 from .diffusion import DiffusiveTendencyPlan, HorizontalScalarDiffusivity, diffusive_tendency, diffusive_tendency_plan
+from .mixing import (ConvectiveAdjustmentVerticalDiffusivity, ExponentialRiDependentTapering, HyperbolicTangentRiDependentTapering,
+                     MixedImplicitStepPlan, PiecewiseLinearRiDependentTapering, RiBasedVerticalDiffusivity, VerticalMixingPlan,
+                     mixed_implicit_step_plan, vertical_mixing_diffusivities, vertical_mixing_plan)
 
 __all__ =["TripolarGrid", "ZipperBoundaryCondition"]
